@@ -1,10 +1,15 @@
 """
 bench.py -- CFR+ node-updates/s on a synthetic Flop5Holdem public tree (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--boards B] [--engine fused|levels] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--boards B] [--engine fused|levels] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 `python bench.py --gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself through torch.distributed.run on
 127.0.0.1 and relays rank 0's JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step and the roofline of the timed
+region itself). --full adds what takes runs of its own: the average-strategy evaluation (roofline_with_avg_evaluation), the
+fixed-problem check, the whole-game lines (N = 1), the --avg-f32 accuracy check and the CPU baseline. --dump-outputs DIR writes
+what the timed path computed in its last step (dump_outputs) as DIR/<name>.npy.
 
 A "step" is one CFRBase.iteration() (reference semantics, PokerRL/cfr/_CFRBase.py:122-134: both seats updated, EVs
 recomputed, current-strategy exploitability available) of CFR+ (delay 0) on the Flop5Holdem betting tree (blinds 50/100,
@@ -18,7 +23,7 @@ bytes over the summed duration of its launches, each bracketed by HIP events on 
 region (prl_solver_time_iterations_ex). "traffic" = HBM bytes per iteration from the rocprofv3 PMC pass in profiles/.
 N > 1: boards sharded over the ranks (one process per GPU), the trunk replicated, one all-gather of the chance node's
 partial sums per EV pass over RCCL (pokerrl_amd/dist.py); weak scaling, value = nodes of the whole tree x iterations / s.
-cpu_baseline: the CPU oracle (plain-C restatement of the reference, 1 thread) on a bounded sample of the same workload --
+cpu_baseline (--full): the CPU oracle (plain-C restatement of the reference, 1 thread) on a bounded sample of the same workload --
 the reference itself cannot run 2-hole-card public trees.
 """
 import argparse
@@ -158,7 +163,7 @@ def fixed_problem_check(total, iters, world, rank, how, lib, emu_lib):
 
 def whole_game_lines(lib, steps, warmup, candidates=1):
     """BASELINE config 3 exactly as stated -- "LinearCFR on Flop Hold'em Poker (1326-combo ranges, full public tree), 1 MI355X" -- and CFR+ on the same tree,
-    as two short HIP-event-timed regions inside the default line (round 5's verdict: the driver should see them): ALL 2 598 960 boards of Flop5Holdem
+    as two short HIP-event-timed regions inside the --full line (round 5's verdict: the driver should see them): ALL 2 598 960 boards of Flop5Holdem
     through their 134 459 suit classes on this one GPU (prl_solver_create_weighted, ~30 GB). Per variant: ms per iteration (device, HIP events on the
     solver's stream), the board pass's share, whole-game iterations/s, the roofline fraction on the class tree's algorithmic bytes, the node-updates/s
     of the class tree and of the full tree it stands for; the average strategy's exploitability after the timed iterations (bit-exact to the oracle's
@@ -204,6 +209,26 @@ def whole_game_lines(lib, steps, warmup, candidates=1):
     return out
 
 
+def dump_outputs(solver, expl, out_dir, seed=0, block=8, budget_bytes=48 << 20):
+    """--dump-outputs: what the timed iterations leave a caller, as float32 / float64 .npy files -- exploitability.npy (the current strategy's, per
+    seat) and, for every per-action-column array the solver holds (regret, avg, avg_sum), the same fixed seeded sample of columns: the first block
+    (the trunk's first columns) and blocks of `block` columns drawn with RandomState(seed), `budget_bytes` in all at most. [columns, range_size]
+    in column order; the same arguments give the same columns. A sharded run (N > 1) dumps rank 0's shard only."""
+    from pokerrl_amd import _native
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "exploitability.npy"), np.asarray(expl, np.float32))
+    n = solver.n_cols
+    n_blocks = -(-n // block)
+    k = max(1, min(n_blocks, budget_bytes // (solver.R * 16 * block)))  # 16 bytes per entry: regret 4 + avg 8 + avg_sum 4
+    picked = np.concatenate([[0], np.sort(1 + np.random.RandomState(seed).choice(n_blocks - 1, k - 1, replace=False))])  # block 0 + k - 1 others
+    for name in ("regret", "avg", "avg_sum"):
+        try:
+            cols = [solver.get_cols(name, int(b) * block, min(block, n - int(b) * block)) for b in picked]
+        except _native.NativeError:  # not held by this variant / average dtype
+            continue
+        np.save(os.path.join(out_dir, name + ".npy"), np.concatenate(cols))
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` outside a launcher: start the N ranks (one process per GPU) the way the driver would."""
     import subprocess
@@ -244,13 +269,20 @@ def main():
                     help="one GPU: do not build a second set of arrays to keep the faster-placed one (DESIGN.md section 4)")
     ap.add_argument("--fixed-check-boards", type=int, default=-1,
                     help="after the timed region: one list of this many boards solved by all ranks together for 3 iterations, exploitability bits in "
-                         "config.fixed_problem_check -- the same in the N = 1, 2, 4, 8 lines (default 8192; 0 = off; the emulator runs of the CPU suite: off unless given)")
+                         "config.fixed_problem_check -- the same in the N = 1, 2, 4, 8 lines (default: 8192 with --full, else off; 0 = off; the emulator "
+                         "runs of the CPU suite: off unless given)")
     ap.add_argument("--no-whole-game-lines", dest="whole_game_lines", action="store_false",
-                    help="N = 1: skip config.whole_game (CFR+ and Linear CFR on the whole game through its suit classes, two short timed regions after the headline)")
+                    help="N = 1, --full: skip config.whole_game (CFR+ and Linear CFR on the whole game through its suit classes, two short timed regions after the headline)")
     ap.add_argument("--whole-game-steps", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-boards", type=int, default=384)
     ap.add_argument("--cpu-iters", type=int, default=24)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: the average-strategy evaluation, the fixed-problem check, the whole-game "
+                         "lines, the --avg-f32 accuracy check, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: what they computed (exploitability, a fixed seeded sample of the regret / average columns) as DIR/<name>.npy; "
+                         "with N > 1 GPUs, rank 0's shard")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -344,8 +376,9 @@ def main():
                                           place=args.placement_candidates if probe else None,
                                           # every candidate is timed the way the headline is: 3 untimed iterations, then as many steady ones as the
                                           # timed region has (HIP events on the solver's stream), so the first allocation's figure below is what a
-                                          # user who does not probe gets, on the headline's own clock
-                                          probe_iters=max(4, args.steps))
+                                          # user who does not probe gets, on the headline's own clock (a plain run: at most 20 of them, so
+                                          # that the probe does not grow with a long timed region)
+                                          probe_iters=max(4, args.steps if args.full else min(args.steps, 20)))
         if solver.placement_ms is not None and solver.engine == "fused":
             placement = [x for x in solver.placement_ms if x > 0.0]
             placement_chosen = solver.placement_chosen
@@ -373,18 +406,23 @@ def main():
         dist.all_gather(allr, mine)
         per_rank = [[float(x) for x in t.tolist()] for t in allr]
         dt = max(r[0] for r in per_rank)
+    expl = solver.exploitability()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(solver, expl, args.dump_outputs)
 
     # the reference's iteration() also evaluates the AVERAGE strategy every time (_CFRBase.py:134,218-262); timed separately
     # (outside the K steps) as one best-response-style evaluation per iteration
-    t1 = time.perf_counter()
-    n_avg = 3
-    for _ in range(n_avg):
-        avg_expl = solver.eval_avg()
-    barrier()
-    avg_eval_ms = (time.perf_counter() - t1) * 1e3 / n_avg
+    avg_expl, avg_eval_ms = None, None
+    if args.full:
+        t1 = time.perf_counter()
+        n_avg = 3
+        for _ in range(n_avg):
+            avg_expl = solver.eval_avg()
+        barrier()
+        avg_eval_ms = (time.perf_counter() - t1) * 1e3 / n_avg
 
     avg_check = None
-    if args.avg_f32 and rank == 0 and not os.environ.get("PRL_BENCH_SKIP_AVG_CHECK"):  # what the float32 storage costs in accuracy (the env knob: profiling runs of the passes alone): both dtypes, the same 4096 boards, 100 iterations
+    if args.full and args.avg_f32 and rank == 0 and not os.environ.get("PRL_BENCH_SKIP_AVG_CHECK"):  # what the float32 storage costs in accuracy (the env knob: profiling runs of the passes alone): both dtypes, the same 4096 boards, 100 iterations
         small = fhp_tree(seeded_boards(4096, 0), lib)
         ev = {}
         for dt_ in ("f64", "f32"):
@@ -396,7 +434,7 @@ def main():
         avg_check = {"boards": 4096, "iterations": 100, "avg_strategy_exploitability_mbb_per_g_f64": ev["f64"], "avg_strategy_exploitability_mbb_per_g_f32": ev["f32"],
                      "relative_difference": abs(ev["f32"] - ev["f64"]) / ev["f64"], "current_strategy_exploitability_mbb_per_g_both": cur}
     fixed = None
-    n_fixed = args.fixed_check_boards if args.fixed_check_boards >= 0 else (0 if emu_lib else 8192)
+    n_fixed = args.fixed_check_boards if args.fixed_check_boards >= 0 else (8192 if args.full and not emu_lib else 0)
     if n_fixed > 0 and n_fixed >= world:
         # (the check's arrays are small beside the run's: 8192 boards = 1.8 GB over all ranks)
         try:  # (an extra after the timed region: whatever goes wrong here must not cost the line)
@@ -406,8 +444,7 @@ def main():
         barrier()
     whole = None
     hbm_allocated, iterations_done, engine_name, n_exchanges = int(solver.get("bytes_allocated")[0]), solver.iter, solver.engine, int(solver.get("exchanges")[0])
-    expl = solver.exploitability()
-    if args.whole_game_lines and not os.environ.get("PRL_BENCH_NO_WHOLE_GAME") and world == 1 and not emu_lib and not args.whole_game and not sharded and not total and args.engine != "levels":
+    if args.full and args.whole_game_lines and not os.environ.get("PRL_BENCH_NO_WHOLE_GAME") and world == 1 and not emu_lib and not args.whole_game and not sharded and not total and args.engine != "levels":
         solver = None  # the headline's 58 GB go back before the whole game's 30 GB come (both would fit; the pass's speed depends on placement)
         try:  # (after the timed region: it must not cost the line)
             whole = whole_game_lines(lib, args.whole_game_steps, 2, args.placement_candidates if args.placement_probe else 1)
@@ -461,8 +498,9 @@ def main():
             "whole_game": whole,
             "iterations_done": iterations_done, "exploitability_mbb_per_g": float(np.mean(expl) * 10.0),
             "exploitability_pinned_to": "oracle/ (C restatement of the reference with an explicit float32 summation order; the reference cannot build 2-hole-card trees)",
-            "avg_strategy_exploitability_mbb_per_g": float(np.mean(avg_expl) * 10.0), "avg_strategy_evaluation_ms": avg_eval_ms,
-            "ms_per_step_with_avg_strategy_evaluation": dt * 1e3 / args.steps + avg_eval_ms,
+            # --full: the average strategy's exploitability and what evaluating it costs (None in a plain run)
+            "avg_strategy_exploitability_mbb_per_g": float(np.mean(avg_expl) * 10.0) if avg_expl is not None else None, "avg_strategy_evaluation_ms": avg_eval_ms,
+            "ms_per_step_with_avg_strategy_evaluation": dt * 1e3 / args.steps + avg_eval_ms if avg_eval_ms is not None else None,
             "hbm_bytes_allocated": hbm_allocated,
             "placement_probe_ms_per_iteration": placement,  # one entry per candidate allocation, built by the library (prl_solver_create_placed): the fastest was kept (None: not probed)
             "placement_chosen": placement_chosen, "first_allocation_probe_ms_per_iteration": placement[0] if placement else None,
@@ -473,8 +511,8 @@ def main():
         },
         # the reference's iteration() also evaluates the AVERAGE strategy every time (_CFRBase.py:134,218-262): the same figure for the
         # iteration WITH that evaluation pass -- algorithmic bytes of the evaluation: the float64 average once + one rank vector per board
-        # (8 R sum(A) + 4 R N_boards), over kernel time of the iteration + the evaluation's wall time
-        "roofline_with_avg_evaluation": {
+        # (8 R sum(A) + 4 R N_boards), over kernel time of the iteration + the evaluation's wall time (--full; None in a plain run)
+        "roofline_with_avg_evaluation": None if avg_eval_ms is None else {
             "bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s",
             "achieved": (bytes_iter + 8.0 * R * sum_a + 4.0 * R * args.boards) / ((kernel_ms / args.steps + avg_eval_ms) * 1e-3) / 1e9,
             "frac": (bytes_iter + 8.0 * R * sum_a + 4.0 * R * args.boards) / ((kernel_ms / args.steps + avg_eval_ms) * 1e-3) / 1e9 / HBM_PEAK_GBPS,
@@ -497,7 +535,7 @@ def main():
                      "achieved_whole_iteration": bytes_iter * args.steps / (dev_ms * 1e-3) / 1e9},
     }
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg is reported at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg is reported at N=1 only
             out["cpu_baseline"] = cpu_baseline(args.cpu_boards, args.cpu_iters)
         import ctypes
         ctypes.CDLL(None).fflush(None)  # RCCL's start-up banner sits in the C stdio buffer: push it out before the JSON line

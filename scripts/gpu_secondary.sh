@@ -8,7 +8,7 @@ run bench_h2h bench_h2h.py
 run bench_handeval bench_handeval.py
 run bench_leduc bench_leduc.py
 run bench_linear bench.py --variant linear --no-cpu-baseline --no-placement-probe
-run bench_avg_f32 bench.py --avg-f32 --no-cpu-baseline
+run bench_avg_f32 bench.py --avg-f32 --no-cpu-baseline --full  # --full: config.avg_f32_check
 python - <<PY
 import json, glob
 for f in sorted(glob.glob("gpurun_out/${TAG}_bench_*.json")):

@@ -123,7 +123,7 @@ def main():
         t0 = time.perf_counter()
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--boards", "32768", "--steps", "3", "--warmup", "1",
-                              "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                              "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
         line = [x for x in out.stdout.splitlines() if x.startswith("{")]
         ok = out.returncode == 0 and len(line) == 1
         j = json.loads(line[0]) if ok else None

@@ -1,7 +1,7 @@
 """SURVEY.md section 8f-1 (batched agent querying) and 8f-2 (EvalAgent pickle): a PyTorch policy agent evaluated by LocalBRMaster
 through the batched protocol (one forward per history length) against the reference protocol (one positioned query per node);
-store_to_disk / load_from_disk round trips; and -- where the reference is present -- a PokerRL-side EvalAgentBase subclass
-evaluated by pokerrl_amd's LocalBRMaster with the reference LocalBRMaster's own result."""
+store_to_disk / load_from_disk round trips; and the hash agent evaluated by pokerrl_amd's LocalBRMaster with the reference
+LocalBRMaster's own result (stored under tests/golden)."""
 import os
 import sys
 
@@ -17,9 +17,6 @@ from pokerrl_amd.game.games import DiscretizedNLLeduc, StandardLeduc  # noqa: E4
 from pokerrl_amd.game.wrappers import FlatLimitPokerEnvBuilder, HistoryEnvBuilder  # noqa: E402
 from pokerrl_amd.rl.base_cls.TrainingProfileBase import TrainingProfileBase  # noqa: E402
 from pokerrl_amd.rl.base_cls.workers.ChiefBase import ChiefBase  # noqa: E402
-
-REF = os.environ.get("POKERRL_REFERENCE", "/root/reference")
-
 
 @pytest.fixture()
 def emu_lib(monkeypatch):
@@ -187,50 +184,23 @@ def test_eval_agent_store_and_load_round_trip(tmp_path):
     assert H.load_from_disk(str(tmp_path / "agents" / "hash.pkl")).get_mode() == "HASH"
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "PokerRL")), reason="the reference does not travel to the GPU box")
 @pytest.mark.parametrize("game_name,bets_name", [("StandardLeduc", None), ("DiscretizedNLLeduc", "POT_ONLY")])
-def test_reference_side_agent_evaluated_by_pokerrl_amd_br_master(emu_lib, tmp_path, game_name, bets_name):
-    """Interop at the plugin surface: the SAME agent class -- a subclass of the REFERENCE's PokerRL.rl.base_cls.EvalAgentBase, with
-    the reference's env wrapper and env inside -- is evaluated by the reference's LocalBRMaster and by pokerrl_amd's LocalBRMaster
-    (which positions it on pokerrl_amd tree nodes through node.parent / node.env_state / node.tree.CHANCE_ID). Equal results."""
-    sys.path.insert(0, os.path.join(HERE, "golden"))
-    import ref_harness
-    ref_harness.setup()
-    import PokerRL.game.bet_sets as ref_bets
-    from PokerRL.eval.br.LocalBRMaster import LocalBRMaster as RefBR
-    from PokerRL.game import games as ref_games
-    from PokerRL.game.wrappers import HistoryEnvBuilder as RefHistoryEnvBuilder
-    from PokerRL.rl.base_cls.EvalAgentBase import EvalAgentBase as RefEvalAgentBase
-    from PokerRL.rl.base_cls.TrainingProfileBase import TrainingProfileBase as RefTProf
-    from PokerRL.rl.base_cls.workers.ChiefBase import ChiefBase as RefChiefBase
+def test_hash_agent_br_value_equals_the_reference_br_masters(emu_lib, tmp_path, game_name, bets_name):
+    """The hash agent (pokerrl_amd.rl.hash_agent, one policy source bound to either package's EvalAgentBase) bound to pokerrl_amd's
+    EvalAgentBase and evaluated by pokerrl_amd's LocalBRMaster gives the value the REFERENCE's LocalBRMaster logged for the same agent class bound to the reference's
+    EvalAgentBase, with the reference's env wrapper and env inside (tests/golden/reference_boundary.json, written by
+    tests/golden/make_reference_boundary_golden.py). Equal results."""
+    import json
+    from pokerrl_amd.game import games
     from pokerrl_amd.rl import hash_agent
-
-    Agent = hash_agent.make_agent_cls(RefEvalAgentBase, seed=7)  # the hash policy: different at every node, hand and action
-    ref_game = getattr(ref_games, game_name)
-    ref_args = ref_game.ARGS_CLS(n_seats=2, bet_sizes_list_as_frac_of_pot=getattr(ref_bets, bets_name)) if bets_name else ref_game.ARGS_CLS(n_seats=2)
-    ref_prof = RefTProf(name="x", log_verbose=False, log_export_freq=1, checkpoint_freq=10 ** 9, eval_agent_export_freq=10 ** 9,
-                        game_cls=ref_game, env_bldr_cls=RefHistoryEnvBuilder, start_chips=None, eval_modes_of_algo=("HASH",),
-                        eval_stack_sizes=None, module_args={"env": ref_args}, path_data=str(tmp_path / "ref"))
-
-    class RefChief(RefChiefBase):
-        def pull_current_eval_strategy(self, last):
-            return None, last
-
-    rc = RefChief(ref_prof)
-    rbr = RefBR(t_prof=ref_prof, chief_handle=rc, eval_agent_cls=Agent)
-    rbr.update_weights()
-    rbr.evaluate(iter_nr=0)
-    (_e, graphs), = rc.get_new_values()[0].items()
-    (_g, series), = graphs.items()
-    want = series[0][1]
-
-    # pokerrl_amd's master, the reference-side agent (it builds its own -- reference -- env from the profile's class names)
-    from pokerrl_amd.eval.br.LocalBRMaster import LocalBRMaster
-    chief = Chief(ref_prof)
-    br = LocalBRMaster(t_prof=ref_prof, chief_handle=chief, eval_agent_cls=Agent)
-    assert isinstance(br._eval_agent, RefEvalAgentBase)
-    br.update_weights()
-    br.evaluate(iter_nr=0)
-    (_e, graphs), = chief.get_new_values()[0].items()
-    (_g, series), = graphs.items()
-    assert series[0][1] == want, (series[0][1], want)
+    from pokerrl_amd.rl.base_cls.EvalAgentBase import EvalAgentBase
+    with open(os.path.join(HERE, "golden", "reference_boundary.json")) as f:
+        want = json.load(f)["br_hash_agent"][game_name]
+    Agent = hash_agent.make_agent_cls(EvalAgentBase, seed=7)  # the hash policy: different at every node, hand and action
+    game = getattr(games, game_name)
+    args = game.ARGS_CLS(n_seats=2, bet_sizes_list_as_frac_of_pot=getattr(bet_sets, bets_name)) if bets_name else game.ARGS_CLS(n_seats=2)
+    prof = TrainingProfileBase(name="x", log_verbose=False, log_export_freq=1, checkpoint_freq=10 ** 9, eval_agent_export_freq=10 ** 9,
+                               game_cls=game, env_bldr_cls=HistoryEnvBuilder, start_chips=None, eval_modes_of_algo=("HASH",),
+                               eval_stack_sizes=None, module_args={"env": args}, path_data=str(tmp_path / "amd"))
+    got, _br = br_of(prof, Agent)
+    assert got == want, (got, want)

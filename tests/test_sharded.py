@@ -177,7 +177,8 @@ def test_bench_gpus_2_launches_two_ranks_gloo_emu(EMU):
     root = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PRL_BENCH_EMU_LIB"] = EMU
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--boards", "2", "--no-cpu-baseline"]
+    # --full: the fixed-problem check and the average strategy's exploitability are part of the --full line
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--boards", "2", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd + ["--fixed-check-boards", "3"], env=env, capture_output=True, text=True, timeout=900, check=True).stdout
     line = [x for x in out.splitlines() if x.startswith("{")]
     assert len(line) == 1, out  # ONE JSON line, printed by rank 0
@@ -185,7 +186,7 @@ def test_bench_gpus_2_launches_two_ranks_gloo_emu(EMU):
     assert j["n_gpus"] == 2 and j["steps"] == 1 and j["scaling"] == "weak"
     assert j["config"]["nodes_whole_tree"] == 5 + 15 * 4 and j["config"]["exchanges"] > 0 and j["config"]["iterations_done"] == 2
     # the two-rank solve of the 4 boards equals the one-rank solve of the same 4 boards
-    one = subprocess.run(cmd[:2] + ["--gpus", "1", "--steps", "1", "--warmup", "1", "--boards", "4", "--no-cpu-baseline", "--fixed-check-boards", "3"], env=env,
+    one = subprocess.run(cmd[:2] + ["--gpus", "1", "--steps", "1", "--warmup", "1", "--boards", "4", "--no-cpu-baseline", "--fixed-check-boards", "3", "--full"], env=env,
                          capture_output=True, text=True, timeout=900, check=True).stdout
     j1 = json.loads([x for x in one.splitlines() if x.startswith("{")][0])
     assert j1["n_gpus"] == 1 and j1["config"]["exchanges"] == 0
@@ -195,15 +196,40 @@ def test_bench_gpus_2_launches_two_ranks_gloo_emu(EMU):
     assert (f1["world"], f2["world"], f1["total_boards"], f2["total_boards"]) == (1, 2, 3, 3)
     assert f1["exploitability_f32_hex"] == f2["exploitability_f32_hex"] and f1["avg_strategy_exploitability_f32_hex"] == f2["avg_strategy_exploitability_f32_hex"]
     # ONE list of 3 boards over two ranks (2 + 1, `--all-boards` in small): strong scaling, same result as the one-rank solve of the 3
-    rag = subprocess.run(cmd[:2] + ["--gpus", "2", "--steps", "1", "--warmup", "1", "--total-boards", "3", "--no-cpu-baseline"], env=env,
+    rag = subprocess.run(cmd[:2] + ["--gpus", "2", "--steps", "1", "--warmup", "1", "--total-boards", "3", "--no-cpu-baseline", "--full"], env=env,
                          capture_output=True, text=True, timeout=900, check=True).stdout
     j2 = json.loads([x for x in rag.splitlines() if x.startswith("{")][0])
-    one3 = subprocess.run(cmd[:2] + ["--gpus", "1", "--steps", "1", "--warmup", "1", "--boards", "3", "--no-cpu-baseline"], env=env,
+    one3 = subprocess.run(cmd[:2] + ["--gpus", "1", "--steps", "1", "--warmup", "1", "--boards", "3", "--no-cpu-baseline", "--full"], env=env,
                           capture_output=True, text=True, timeout=900, check=True).stdout
     j3 = json.loads([x for x in one3.splitlines() if x.startswith("{")][0])
     assert j2["n_gpus"] == 2 and j2["scaling"] == "strong" and j2["config"]["nodes_whole_tree"] == 5 + 15 * 3 == j3["config"]["nodes_whole_tree"]
     assert j2["config"]["exploitability_mbb_per_g"] == j3["config"]["exploitability_mbb_per_g"]
     assert j2["config"]["avg_strategy_exploitability_mbb_per_g"] == j3["config"]["avg_strategy_exploitability_mbb_per_g"]
+
+
+def test_bench_dump_outputs_emu(EMU, tmp_path):
+    """`bench.py --dump-outputs DIR`: what the timed steps computed, as float32 / float64 .npy files (a fixed seeded sample of the columns, 64 MB at
+    most), the same from run to run; --steps sets the number of timed iterations and the plain line carries ms_per_step. Emulator build, one rank."""
+    import json
+    root = os.path.dirname(HERE)
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["PRL_BENCH_EMU_LIB"] = EMU
+    runs = []
+    for name in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--boards", "5",
+                              "--dump-outputs", str(tmp_path / name)], env=env, capture_output=True, text=True, timeout=900, check=True).stdout
+        j = json.loads([x for x in out.splitlines() if x.startswith("{")][0])
+        assert j["steps"] == 3 and j["config"]["iterations_done"] == 4 and j["ms_per_step"] > 0
+        assert "cpu_baseline" not in j and j["config"]["whole_game"] is None and j["config"]["fixed_problem_check"] is None  # --full only
+        files = sorted(os.listdir(tmp_path / name))
+        assert "exploitability.npy" in files and "regret.npy" in files, files
+        arrays = {f: np.load(tmp_path / name / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["regret.npy"].shape == (j["config"]["action_columns_per_gpu"], 1326)  # a small tree fits the budget: every column
+        assert np.float32(j["config"]["exploitability_mbb_per_g"]) == np.float32(np.mean(arrays["exploitability.npy"]) * 10.0)
+        runs.append(arrays)
+    assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][f], runs[1][f]) for f in runs[0])
 
 
 def test_bench_br_gpus_2_launches_two_ranks_gloo_emu(EMU):
