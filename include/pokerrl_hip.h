@@ -193,6 +193,35 @@ int32_t prl_tree_get(const prl_tree_t* tree, int32_t field, int32_t* out);
  * not dealt yet = -1); for a game that deals once these are the caller's rows */
 int32_t prl_tree_get_boards(const prl_tree_t* tree, int8_t* out_rows);
 
+/* Observations of public-tree nodes, computed on the GPU: for each requested decision node, what
+ * `wrapper.set_to_public_tree_node_state(node); wrapper.get_current_obs()` returns (PokerRL/game/_/wrappers/: RecurrentHistoryWrapper.py:57-85,
+ * FlatHULimitPokerHistoryWrapper.py:93-114, Vanilla.py), bit for bit, plus the node's legal-action mask.
+ *   PRL_OBS_VANILLA        one row: the node's env observation (row_dim = obs_dim)
+ *   PRL_OBS_HISTORY        hist_len rows: the observation of every decision node on the root path (chance nodes skipped), root first, or the
+ *                          node first with `invert` (HistoryEnvBuilder(invert_history_order=True)); row_dim = obs_dim
+ *   PRL_OBS_FLAT_HU_LIMIT  one row: the env observation, then the one-hot action-history vector (fixed-limit games only); row_dim = obs_dim +
+ *                          the vector's size; flat_offsets = [n_rounds] round offsets then [n_rounds] half-round sizes of the vector
+ *                          (FlatLimitPokerEnvBuilder._VEC_ROUND_OFFSETS, _VEC_HALF_ROUND_SIZE; at most 128 entries)
+ * obs_dim is the heads-up env observation's length (7 + 3 + 2 + 2 + n_rounds + 6 + n_board_cards * (n_ranks + n_suits)).
+ * The env state of every node is computed once per tree on the GPU (one launch per level) and kept with the tree until prl_tree_destroy. */
+#define PRL_OBS_VANILLA 0
+#define PRL_OBS_HISTORY 1
+#define PRL_OBS_FLAT_HU_LIMIT 2
+/* per requested node (host arrays): the number of decision nodes on its root path, itself included (the history's length) */
+int32_t prl_tree_obs_hist_len(const prl_tree_t* tree, const int32_t* node_idx, int32_t n, int32_t* out_hist_len);
+/* node_idx, row_offset: host arrays of n entries (checked, then uploaded). Request i's rows (hist_len of them for PRL_OBS_HISTORY, else one) go to
+ * d_out + (row_offset[i] + k) * row_dim, k = 0 .. rows - 1; d_out holds n_rows rows of row_dim floats. d_legal (may be NULL): uint8 [n][n_actions],
+ * 1 where the action int is legal at node i. d_out and d_legal are device pointers. Returns PRL_ERR_ARG (prl_last_error set, nothing launched) for
+ * an index out of range or not a decision node, a row past n_rows, a row_dim that does not fit `kind`, PRL_OBS_FLAT_HU_LIMIT on a game that is not
+ * fixed-limit, or a partial tree. Works on the tree's own stream and returns after it has finished; the caller synchronises whatever last used
+ * d_out / d_legal (another stream, a caching allocator's earlier owner) before the call. */
+int32_t prl_tree_observations_device(const prl_tree_t* tree, int32_t kind, int32_t invert, const int32_t* node_idx, const int64_t* row_offset,
+                                     int32_t n, const int32_t* flat_offsets, int32_t row_dim, int64_t n_rows, float* d_out, uint8_t* d_legal,
+                                     int32_t n_actions);
+/* out[4]: bytes of the tree's env-state cache, milliseconds of its build (HIP events), of the last prl_tree_observations_device's kernels, and the
+ * bytes those kernels wrote */
+int32_t prl_tree_obs_stats(const prl_tree_t* tree, double* out);
+
 
 /* ---------------------------------------------------------------------------------------------------------------- */
 /* 4. Heads-up betting engine, one env on the host (tree construction, tests, Python PokerEnv facade).                 */

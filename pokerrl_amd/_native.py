@@ -548,6 +548,37 @@ class NativeTree:
             self._cache[name] = out
         return self._cache[name]
 
+    def obs_hist_len(self, node_idx):
+        """int32 [n]: decision nodes on each requested decision node's root path, itself included (prl_tree_obs_hist_len)"""
+        idx = np.ascontiguousarray(node_idx, dtype=np.int32)
+        out = np.empty(len(idx), np.int32)
+        self._L.prl_tree_obs_hist_len.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+        self._L.prl_tree_obs_hist_len.restype = ctypes.c_int32
+        check(self._L.prl_tree_obs_hist_len(self._h, _ptr(idx), len(idx), _ptr(out)), self._L)
+        return out
+
+    def observations_device(self, kind, invert, node_idx, row_offset, flat_offsets, row_dim, n_rows, d_out, d_legal, n_actions):
+        """prl_tree_observations_device: the requested nodes' observation rows to d_out (float32 [n_rows, row_dim]) and their legal masks to d_legal
+        (uint8 [n, n_actions], 0 = none), device addresses; returns when the library's stream is done"""
+        idx = np.ascontiguousarray(node_idx, dtype=np.int32)
+        off = np.ascontiguousarray(row_offset, dtype=np.int64)
+        assert len(off) == len(idx)
+        fo = None if flat_offsets is None else np.ascontiguousarray(flat_offsets, dtype=np.int32)
+        L = self._L
+        L.prl_tree_observations_device.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                                   ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
+        L.prl_tree_observations_device.restype = ctypes.c_int32
+        check(L.prl_tree_observations_device(self._h, int(kind), 1 if invert else 0, _ptr(idx), _ptr(off), len(idx), None if fo is None else _ptr(fo),
+                                              int(row_dim), int(n_rows), ctypes.c_void_p(int(d_out)), ctypes.c_void_p(int(d_legal or 0)), int(n_actions)), L)
+
+    def obs_stats(self):
+        """{state_bytes, states_ms, obs_ms, obs_bytes}: the env-state cache and the last observation call's kernels (prl_tree_obs_stats)"""
+        out = np.zeros(4, np.float64)
+        self._L.prl_tree_obs_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._L.prl_tree_obs_stats.restype = ctypes.c_int32
+        check(self._L.prl_tree_obs_stats(self._h, _ptr(out)), self._L)
+        return dict(state_bytes=int(out[0]), states_ms=float(out[1]), obs_ms=float(out[2]), obs_bytes=int(out[3]))
+
     def __del__(self):
         try:
             if self._h:
@@ -556,6 +587,9 @@ class NativeTree:
         except Exception:
             pass
 
+
+# observation kinds of prl_tree_observations_device (include/pokerrl_hip.h)
+OBS_VANILLA, OBS_HISTORY, OBS_FLAT_HU_LIMIT = 0, 1, 2
 
 # solver field ids (include/pokerrl_hip.h)
 SF = dict(reach=0, ev=1, ev_br=2, strategy=3, strat_f64=4, regret=5, avg=6, avg_f64=7, avg_sum=8, br_idx=9,

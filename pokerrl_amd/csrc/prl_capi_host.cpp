@@ -122,10 +122,6 @@ int32_t prl_lut_card_in_what_range_idxs(const PrlRules* rules, int32_t* out) {
 int32_t prl_hand_rank_7(const int8_t* board_1d, int8_t c1, int8_t c2) { return prl_rank7_cards_52(board_1d, c1, c2); }
 
 // ---- public tree -----------------------------------------------------------------------------------------------------
-struct prl_tree {
-    PrlFlatTree t;
-};
-
 int32_t prl_tree_build(const PrlGame* game, const PrlRules* rules, const int8_t* boards, int32_t n_boards,
                        int32_t board_len, prl_tree_t** out_tree) {
     return prl_tree_build_partial(game, rules, boards, n_boards, board_len, -1, out_tree);
@@ -147,7 +143,10 @@ int32_t prl_tree_build_partial(const PrlGame* game, const PrlRules* rules, const
     return PRL_OK;
 }
 
-void prl_tree_destroy(prl_tree_t* tree) { delete tree; }
+void prl_tree_destroy(prl_tree_t* tree) {
+    if (tree) prl_tree_obs_free(tree->obs);
+    delete tree;
+}
 
 const PrlFlatTree* prl_tree_flat(const prl_tree_t* tree) { return tree ? &tree->t : nullptr; }
 

@@ -12,6 +12,8 @@ legal actions only -- the passes (fill / reach / ev) need the whole tree and rai
 For 2-hole-card games the chance outcomes must be given (`boards=`): the reference cannot enumerate them at all
  and the full C(52,5) set does not fit one GPU.
 """
+from collections.abc import Sequence
+
 import numpy as np
 
 from pokerrl_amd import _native
@@ -20,6 +22,36 @@ from pokerrl_amd.game.Poker import Poker
 from pokerrl_amd.game.PokerEnvStateDictEnums import EnvDictIdxs, PlayerDictIdxs
 
 KIND_DECISION, KIND_CHANCE, KIND_FOLD, KIND_SHOWDOWN = 0, 1, 2, 3
+
+
+class DecisionNodes(Sequence):
+    """The decision nodes of one tree in DFS pre-order (the order prl_solver_set_strategy_device expects), as a lazy sequence: `node_idx` (int32)
+    holds their ids and a TreeNode is made only when an element is indexed. Agents that work on the ids (TorchPolicyAgent's device path:
+    PublicTree.node_observations) never make one."""
+
+    def __init__(self, tree, node_idx):
+        self.tree = tree
+        self.node_idx = node_idx
+
+    def __len__(self):
+        return len(self.node_idx)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self.tree.node(int(n)) for n in self.node_idx[i]]
+        return self.tree.node(int(self.node_idx[i]))
+
+    def __iter__(self):
+        return (self.tree.node(int(n)) for n in self.node_idx)
+
+
+class NodeObservations:
+    """PublicTree.node_observations: the requested nodes' observations grouped by history shape, as TorchPolicyAgent batches them.
+    groups: [(positions, obs)] in first-appearance order of the shape -- positions (int64, into the request, in request order) and obs, a view of
+    one device buffer: [n_g, T, D] (HistoryEnvBuilder) or [n_g, D] (Vanilla / Flat). legal: bool [n, N_ACTIONS]; hist_len: int32 [n] (host)."""
+
+    def __init__(self, groups, legal, hist_len, buffer):
+        self.groups, self.legal, self.hist_len, self.buffer = groups, legal, hist_len, buffer
 
 
 class TreeNode:
@@ -231,6 +263,64 @@ class PublicTree:
     def nodes(self):
         return (self.node(i) for i in range(self._native_tree.n_nodes))
 
+    def decision_nodes(self):
+        """lazy view of the decision nodes in DFS pre-order (DecisionNodes)"""
+        return DecisionNodes(self, np.flatnonzero(self._kind == KIND_DECISION).astype(np.int32))
+
+    def node_observations(self, env_bldr, node_idx=None, device=None):
+        """What `wrapper.set_to_public_tree_node_state(node); wrapper.get_current_obs()` returns for each requested decision node (default: all of
+        them, DFS pre-order), and the nodes' legal-action masks, computed by the library's kernels (prl_tree_observations_device) into tensors on
+        `device` -- where the bound library writes: the GPU for the HIP build (default "cuda"), host memory for the emulator build ("cpu").
+        Equal, bit for bit, to wrappers.history_of_nodes. Grouped as TorchPolicyAgent._fill_nodes groups (NodeObservations)."""
+        import torch
+        from pokerrl_amd.game import wrappers as W
+        t = self._native_tree
+        if node_idx is None:
+            node_idx = np.flatnonzero(self._kind == KIND_DECISION)
+        idx = np.ascontiguousarray(node_idx, dtype=np.int32)
+        on_gpu = _native.build_flavor().startswith("hip")
+        device = torch.device(device if device is not None else ("cuda" if on_gpu else "cpu"))
+        if (device.type == "cuda") != on_gpu:
+            raise ValueError("node_observations: the %s library writes %s memory, not %s" % (_native.build_flavor(), "device" if on_gpu else "host", device))
+        D, flat_offsets, invert = env_bldr.pub_obs_size, None, False
+        if isinstance(env_bldr, W.HistoryEnvBuilder):
+            kind, invert = _native.OBS_HISTORY, bool(env_bldr.invert_history_order)
+        elif isinstance(env_bldr, W.FlatLimitPokerEnvBuilder):
+            kind = _native.OBS_FLAT_HU_LIMIT
+            rounds = sorted(env_bldr._VEC_ROUND_OFFSETS)
+            flat_offsets = [env_bldr._VEC_ROUND_OFFSETS[r] for r in rounds] + [env_bldr._VEC_HALF_ROUND_SIZE[r] for r in rounds]
+        else:
+            kind = _native.OBS_VANILLA
+        hist_len = t.obs_hist_len(idx)
+        T = hist_len if kind == _native.OBS_HISTORY else np.ones(len(idx), np.int32)
+        # groups: one per history length, in first-appearance order; rows of a group are contiguous, nodes in request order
+        uniq, first, inv = np.unique(T, return_index=True, return_inverse=True)
+        order = np.argsort(first)
+        shapes = uniq[order]
+        gid = np.empty(len(uniq), np.int64)
+        gid[order] = np.arange(len(uniq))
+        g_of = gid[inv.reshape(-1)]
+        counts = np.bincount(g_of, minlength=len(shapes)).astype(np.int64)
+        base = np.concatenate(([0], np.cumsum(counts * shapes.astype(np.int64))))
+        perm = np.argsort(g_of, kind="stable")
+        start = np.concatenate(([0], np.cumsum(counts)))
+        rank = np.empty(len(idx), np.int64)
+        rank[perm] = np.arange(len(idx)) - start[g_of[perm]]
+        row_offset = base[g_of] + rank * T.astype(np.int64)
+        n_rows = int(base[-1])
+        A = int(env_bldr.N_ACTIONS)
+        out = torch.empty((max(n_rows, 1), D), dtype=torch.float32, device=device)
+        legal = torch.empty((len(idx), A), dtype=torch.uint8, device=device)
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)  # the buffers' earlier owners (caching allocator) are done with them
+        t.observations_device(kind, invert, idx, row_offset, flat_offsets, D, n_rows, out.data_ptr(), legal.data_ptr() if len(idx) else 0, A)
+        groups = []
+        for g, Tg in enumerate(shapes):
+            pos = perm[start[g]:start[g + 1]]
+            blk = out[base[g]:base[g + 1]]
+            groups.append((pos, blk.view(int(counts[g]), int(Tg), D) if kind == _native.OBS_HISTORY else blk))
+        return NodeObservations(groups, legal.bool(), hist_len, out)
+
     @property
     def solver(self):
         if self._solver is None:
@@ -270,17 +360,19 @@ class PublicTree:
 
         An agent that defines ``get_a_probs_for_each_hand_in_nodes_device(nodes)`` -> a float32 device tensor ``[len(nodes), RANGE_SIZE, N_ACTIONS]``
         (or None to decline) keeps the probabilities in HBM: no host copy of the strategy at all (prl_solver_set_strategy_device).
+        Both batched protocols receive `decision_nodes()`, a lazy sequence: a TreeNode is made only for an element the agent indexes.
         SURVEY section 8f-1 (batched agent querying): an agent that defines
         ``get_a_probs_for_each_hand_in_nodes(nodes) -> [len(nodes), RANGE_SIZE, N_ACTIONS]`` is asked ONCE for all decision
         nodes (DFS pre-order, the order the reference visits them in) instead of once per node, so a neural agent can run
         one batched forward; it positions its own env copies from ``node.env_state`` / the node's action history."""
         t = self._native_tree
         decision = np.where(self._kind == KIND_DECISION)[0]
+        view = self.decision_nodes()  # lazy: an agent that works on node ids (TorchPolicyAgent's device path) makes no TreeNode at all
         on_device = getattr(agent, "get_a_probs_for_each_hand_in_nodes_device", None)
         if callable(on_device):
             # round 6: the probabilities never leave HBM -- a float32 tensor [n_decision_nodes, R, N_ACTIONS] on the GPU (the network's output) is
             # scattered into the solver's columns by the library (prl_solver_set_strategy_device); equal to the host path below bit for bit
-            probs = on_device([self.node(int(n)) for n in decision])
+            probs = on_device(view)
             if probs is not None:
                 assert tuple(probs.shape) == (len(decision), t.range_size, int(self._env_bldr.N_ACTIONS)) and probs.is_contiguous(), tuple(probs.shape)
                 self._staged.clear()
@@ -290,7 +382,7 @@ class PublicTree:
         strat, dtype = np.zeros((t.n_cols, t.range_size), np.float64), None
         batched = getattr(agent, "get_a_probs_for_each_hand_in_nodes", None)
         if callable(batched):
-            nodes = [self.node(int(n)) for n in decision]
+            nodes = view
             probs = np.asarray(batched(nodes))
             assert probs.shape[:2] == (len(nodes), t.range_size), probs.shape
             for n, node, pr in zip(decision, nodes, probs):

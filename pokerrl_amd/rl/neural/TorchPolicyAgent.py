@@ -10,6 +10,8 @@ cost of a best-response evaluation. Here
     tree (wrappers.history_of_nodes), nodes with the same history length are stacked, and the network runs ONE forward per
     length: public trunk [n_nodes, T, pub_obs] -> [n_nodes, H], private trunk [RANGE_SIZE, priv_obs] -> [R, H] once, head on the
     [n_nodes, R] cross product. PublicTree.fill_with_agent_policy picks this up automatically.
+  * `get_a_probs_for_each_hand_in_nodes_device(nodes)` keeps inputs and outputs on the device: the observations and legal masks come from the
+    library's kernels (PublicTree.node_observations, bit for bit the host walk's), the same groups and chunks feed the same forwards.
 The network is a plain module (GRU or MLP public trunk + linear private trunk + MLP head, softmax over the legal actions); weights
 come from `update_weights(state_dict)` / the agent pickle. It stands for the neural agents of the reference's downstream projects
 (Deep CFR, NFSP: PokerRL/rl/neural/*): those are out of this repository's scope, this class is what exercises the path.
@@ -119,10 +121,36 @@ class TorchPolicyAgent(EvalAgentBase):
             return None
         R, A = self.env_bldr.rules.RANGE_SIZE, self.env_bldr.N_ACTIONS
         out = torch.zeros((len(nodes), R, A), dtype=torch.float32, device=self.device)
-        self._fill_nodes(nodes, lambda part, probs: out.index_copy_(0, torch.as_tensor(part, device=self.device), probs), self._forward_t)
+        if self._library_writes_here():
+            self._fill_nodes_from_tree(nodes, out)
+        else:
+            self._fill_nodes(nodes, lambda part, probs: out.index_copy_(0, torch.as_tensor(part, device=self.device), probs), self._forward_t)
         if out.is_cuda:
             torch.cuda.synchronize(out.device)
         return out
+
+    def _library_writes_here(self):
+        """the bound library's kernels write where this agent's tensors live: the HIP build and a cuda agent, or the emulator build (tests) and a
+        CPU agent. Then the observations come from PublicTree.node_observations; otherwise from the host walk (wrappers.history_of_nodes)."""
+        from pokerrl_amd import _native
+        on_gpu = _native.build_flavor().startswith("hip")
+        return (torch.device(self.device).type == "cuda") == on_gpu
+
+    @torch.no_grad()
+    def _fill_nodes_from_tree(self, nodes, out):
+        """_fill_nodes with the observations and legal masks built by the library's kernels (PublicTree.node_observations): the same groups, the
+        same chunks, the same input bits -- so the same forwards and the same output"""
+        if hasattr(nodes, "node_idx"):  # PublicTree.decision_nodes(): no TreeNode objects
+            tree, node_idx = nodes.tree, nodes.node_idx
+        else:
+            tree, node_idx = nodes[0].tree, np.array([n._i for n in nodes], np.int32)
+        obs = tree.node_observations(self.env_bldr, node_idx, device=self.device)
+        chunk = max(1, self.MAX_ROWS_PER_FORWARD // self.env_bldr.rules.RANGE_SIZE)
+        for positions, x in obs.groups:
+            for lo in range(0, len(positions), chunk):
+                part = torch.as_tensor(positions[lo:lo + chunk], device=self.device)
+                self.n_forwards += 1
+                out.index_copy_(0, part, self._net(x[lo:lo + chunk], self._priv, obs.legal.index_select(0, part)).float())
 
     def get_a_probs_for_each_hand_in_nodes(self, nodes):
         """float32 [len(nodes), RANGE_SIZE, N_ACTIONS] for decision nodes of one PublicTree: one forward per history length"""
