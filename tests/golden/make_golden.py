@@ -2,7 +2,7 @@
 Generates the golden fixtures under tests/golden/ by RUNNING THE REFERENCE (/root/reference, read-only) in this
 container. The fixtures travel to the GPU box; the reference does not.
 
-    python tests/golden/make_golden.py [luts] [handrank] [handrank_exhaustive] [tree] [tree_lh] [env] [cfr] [br]
+    python tests/golden/make_golden.py [luts] [handrank] [handrank_exhaustive] [tree] [tree_lh] [tree_lh_runouts] [env] [cfr] [env_obs] [indep]
 
 Everything is deterministic (fixed seeds); numpy version is recorded in every file because the reference's float32
 results depend on NumPy-2 promotion rules (SURVEY.md section 8a "dtype ledger").
@@ -403,6 +403,34 @@ def make_tree_limit_holdem_runouts():
     save("tree_LimitHoldem_2x2x2.npz", runouts=ro, **flat)
 
 
+# case -> (game class, stack, bet set, run-outs F x T x R of tests/parity_cases.multistreet_runouts)
+INDEP_CASES = {
+    "nl600": (DiscretizedNLHoldem, 600, bet_sets.POT_ONLY, (2, 2, 2)),
+    "nl20000": (DiscretizedNLHoldem, 20000, bet_sets.POT_ONLY, (1, 2, 2)),
+    "lh6": (LimitHoldem, 6, None, (2, 2, 2)),
+    "lh48": (LimitHoldem, 48, None, (1, 2, 2)),
+}
+
+
+def make_indep():
+    """Inputs of the independent solver's run-out cases (tests/independent_fhp.py, tests/test_independent_runouts.py), one indep_<case>.npz each:
+    the betting template of the reference env (walk_env_tree: one child per chance node, an all-in call a SHOWDOWN below an incomplete board),
+    the run-out rows (stored, not recomputed), the reference's rank of every hand on every row and its hole-card table"""
+    sys.path.insert(0, os.path.dirname(HERE))                     # tests/
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))    # the repository root
+    import parity_cases as pc
+    sys.setrecursionlimit(20000)
+    for case, (cls, stack, bets, fxr) in INDEP_CASES.items():
+        flat = walk_env_tree(cls, stack, bets)
+        ro = pc.multistreet_runouts(*fxr)
+        lh = cls.get_lut_holder()
+        ranks = cls.RULES().get_hand_rank_all_hands_on_given_boards(boards_1d=ro, lut_holder=lh)
+        assert ranks.shape == (len(ro), 1326) and ranks.dtype == np.int32
+        print(case, "template nodes", len(flat["kind"]), "run-outs", len(ro))
+        save("indep_%s.npz" % case, runouts=ro, ranks=ranks, hole_cards=np.asarray(lh.LUT_IDX_2_HOLE_CARDS, np.int8),
+             stack=np.array(stack, np.int32), **{"tpl_" + k: v for k, v in flat.items()})
+
+
 ENV_FUZZ = {
     "StandardLeduc": (StandardLeduc, 13, [0.0]),
     "BigLeduc": (BigLeduc, 100, [0.0]),
@@ -639,7 +667,8 @@ def make_env_obs():
 if __name__ == "__main__":
     what = sys.argv[1:] or ["luts", "handrank", "tree", "env", "cfr"]
     fns = {"luts": make_luts, "handrank": make_handrank, "handrank_exhaustive": make_handrank_exhaustive,
-           "tree": make_tree, "tree_lh": make_tree_limit_holdem, "tree_lh_runouts": make_tree_limit_holdem_runouts, "env": make_env, "cfr": make_cfr, "env_obs": make_env_obs}
+           "tree": make_tree, "tree_lh": make_tree_limit_holdem, "tree_lh_runouts": make_tree_limit_holdem_runouts, "env": make_env, "cfr": make_cfr, "env_obs": make_env_obs,
+           "indep": make_indep}
     i = 0
     while i < len(what):
         w = what[i]

@@ -15,13 +15,34 @@ The game (reference semantics, generalised the only way that collapses to first 
   * terminal utility of seat p: +-main_pot/2 (fold: the folder loses, ValueFiller.py:112; showdown: higher rank wins, ties 0, :145-155), 0 for a
     hand that shares a card with the board (:57-59); main_pot as the reference env reports it before the money moves (PublicTree.py:244-251)
   * ev[p][h] = E[utility | own hand h] under the strategy profile; best response = max over own actions per hand; exploitability[p] = sum_h P(h) (br - ev)[h]
+  * an all-in call ends the betting below an incomplete board (the env runs the board out inside the step): its SHOWDOWN node is the expectation
+    over the listed continuations of that board prefix, dealt street by street with the chance-node weight above (prior 1/nc of the
+    continuations listed at that prefix, times C(left, k) / C(left-4, k)), each completed board paying +-main_pot/2 with the main_pot recorded
+    at the all-in node
   * CFR+ as CFRPlus.py:37-87 / _CFRBase.py:122-134: seat 0 then seat 1, each on freshly computed values; regrets clamped at 0; unweighted blend average.
+
+Inputs of the multi-deal cases (tests/golden/indep_<case>.npz, `make_golden.py indep`): the betting template walked out of the reference env
+(one child per chance node), the run-out rows (deals = the distinct continuations of every prefix in row order, deals_of_runouts), the
+reference evaluator's rank of every hand on every row and the reference's hole-card table.
 """
 from math import comb
 
 import numpy as np
 
 DECISION, CHANCE, FOLD, SHOWDOWN = 0, 1, 2, 3
+
+
+def deals_of_runouts(rows, streets=(3, 1, 1)):
+    """{board prefix: [cards dealt next, one tuple per distinct continuation, in row order]} of full run-out rows dealt `streets` cards at a time"""
+    deals = {}
+    for r in rows:
+        r, n = tuple(int(c) for c in r), 0
+        for k in streets:
+            outs = deals.setdefault(r[:n], [])
+            if r[n:n + k] not in outs:
+                outs.append(r[n:n + k])
+            n += k
+    return deals
 
 
 class IndependentSolver:
@@ -38,6 +59,7 @@ class IndependentSolver:
         h = self.hole
         self.disjoint = (h[:, None, :, None] != h[None, :, None, :]).all(axis=(2, 3)).astype(np.float64)  # [R, R] hands that share no card
         self.deals, self.ranks, self.delay = deals, ranks_of_board, delay
+        self.n_board = max(len(b) + len(o) for b, outs in deals.items() for o in outs)
         self.regret, self.sigma, self.avg, self.iter, self._mats = {}, {}, {}, 0, {}
 
     def matrix(self, kind, board):
@@ -52,24 +74,37 @@ class IndependentSolver:
             self._mats[key] = m
         return self._mats[key]
 
+    def outcome_weight(self, b, o):
+        """chance weight of dealing the cards o onto the board b: prior 1 / (outcomes listed at b) times the likelihood ratio for two untouched hands"""
+        left = 52 - len(b)
+        return comb(left, len(o)) / comb(left - 4, len(o)) / len(self.deals[b])
+
+    def completions(self, b):
+        """[(completed board, weight)] of the listed run-outs below the prefix b, in deal order (an all-in showdown: street by street)"""
+        if len(b) == self.n_board:
+            return [(b, 1.0)]
+        return [(f, self.outcome_weight(b, o) * w) for o in self.deals[b] for f, w in self.completions(b + tuple(o))]
+
     def strategy(self, table, n, b):
         a = len(self.kids[n])
         return table.get((n, b), np.full((self.R, a), 1.0 / a))
 
-    def evaluate(self, table, seat=None):
-        """root (ev[2,R], br[2,R]) of the profile `table`; with seat: also {(node, board): instantaneous regrets [R, A]} of that seat's nodes"""
+    def evaluate(self, table, seat=None, nodes=None):
+        """root (ev[2,R], br[2,R]) of the profile `table`; with seat: also {(node, board): instantaneous regrets [R, A]} of that seat's nodes;
+        a dict `nodes` receives every node's (ev[2,R], br[2,R]) keyed by (template node, board prefix)"""
         terms = []
 
         def down(n, b, w, pi):
             k = self.kind[n]
-            if k >= FOLD:
+            if k == FOLD:
                 terms.append((n, b, w, pi))
+            elif k == SHOWDOWN:  # below an incomplete board: an all-in call, run out over the listed continuations
+                for f, wf in self.completions(b):
+                    terms.append((n, f, w * wf, pi))
             elif k == CHANCE:
                 assert len(self.kids[n]) == 1
-                outs = self.deals[b]
-                for o in outs:
-                    left = 52 - len(b)
-                    down(self.kids[n][0], b + tuple(o), w * comb(left, len(o)) / comb(left - 4, len(o)) / len(outs), pi)
+                for o in self.deals[b]:
+                    down(self.kids[n][0], b + tuple(o), w * self.outcome_weight(b, o), pi)
             else:
                 s = self.strategy(table, n, b)
                 for a, c in enumerate(self.kids[n]):
@@ -98,20 +133,23 @@ class IndependentSolver:
         def up(n, b):
             k = self.kind[n]
             if k >= FOLD:
-                v = next(it)
-                return v, v
-            if k == CHANCE:
+                v = next(it) if k == FOLD else sum(next(it) for _ in self.completions(b))
+                ev, br = v, v
+            elif k == CHANCE:
                 res = [up(self.kids[n][0], b + tuple(o)) for o in self.deals[b]]
-                return sum(r[0] for r in res), sum(r[1] for r in res)
-            p, s = self.actor[n], self.strategy(table, n, b)
-            res = [up(c, b) for c in self.kids[n]]
-            ev, br = np.zeros((2, self.R)), np.zeros((2, self.R))
-            ev[p] = sum(s[:, a] * r[0][p] for a, r in enumerate(res))
-            ev[1 - p] = sum(r[0][1 - p] for r in res)
-            br[p] = np.max([r[1][p] for r in res], axis=0)
-            br[1 - p] = sum(r[1][1 - p] for r in res)
-            if p == seat:
-                inst[(n, b)] = np.stack([r[0][p] for r in res], axis=1) - ev[p][:, None]
+                ev, br = sum(r[0] for r in res), sum(r[1] for r in res)
+            else:
+                p, s = self.actor[n], self.strategy(table, n, b)
+                res = [up(c, b) for c in self.kids[n]]
+                ev, br = np.zeros((2, self.R)), np.zeros((2, self.R))
+                ev[p] = sum(s[:, a] * r[0][p] for a, r in enumerate(res))
+                ev[1 - p] = sum(r[0][1 - p] for r in res)
+                br[p] = np.max([r[1][p] for r in res], axis=0)
+                br[1 - p] = sum(r[1][1 - p] for r in res)
+                if p == seat:
+                    inst[(n, b)] = np.stack([r[0][p] for r in res], axis=1) - ev[p][:, None]
+            if nodes is not None:
+                nodes[(n, b)] = (ev, br)
             return ev, br
 
         ev, br = up(0, ())

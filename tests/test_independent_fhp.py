@@ -116,6 +116,23 @@ def test_independent_solver_is_self_consistent():
     always_fold = {(0, ()): np.tile([1.0, 0.0], (ind.R, 1))}    # SB folds pre-flop with every hand: BB wins the 50 of `main_pot 100 / 2`
     ev, _, _ = ind.evaluate(always_fold)
     assert np.allclose(ev[1], 50.0, rtol=0, atol=1e-9) and np.allclose(ev[0], -50.0, rtol=0, atol=1e-9)
+    # the chance weights of a run-out dealt street by street (all-in calls): with every remaining card listed, the completed boards that touch
+    # neither of two disjoint hands carry a total weight of exactly 1 (1 / C(52-n_b-4, k) per outcome) -- under one turn, and under one flop
+    flop, turn = (3, 17, 40), (22,)
+    rest = [c for c in range(52) if c not in flop]
+    deals = {flop: [(c,) for c in rest]}
+    deals.update({flop + (c,): [(r,) for r in rest if r != c] for c in rest})
+    ind = IndependentSolver(golden("tree_Flop5Holdem_1board.npz"), ind.hole, deals, {})
+    rng = np.random.RandomState(3)
+    for prefix in (flop + turn, flop):
+        done = ind.completions(prefix)
+        assert len(done) == (48 if len(prefix) == 4 else 49 * 48)
+        hands = [set(h) for h in ind.hole[rng.permutation(ind.R)] if not set(h) & set(prefix)]
+        pairs = [(h, h2) for h, h2 in zip(hands[0::2], hands[1::2]) if not h & h2][:20]
+        assert len(pairs) == 20
+        for h, h2 in pairs:
+            mass = sum(w for b, w in done if not set(b) & (h | h2))
+            assert abs(mass - 1.0) < 1e-12, (prefix, h, h2, mass)
 
 
 def _oracle(case, t):
