@@ -177,6 +177,7 @@ const PrlFhpShapeDesc& prl_fhp_shape_desc(int shape_id);  // prl_fhp_kernels.hip
 // [n_boards][n_cols_board][np]; the trunk's columns stay [R] in hand order in front of them. prl_solver_get / set / checkpoints translate
 // (prl_launch_fhp_expand / _compact).
 #define PRL_FHP_NP 1088
+enum { PRL_FHP_AVG_NORMAL = 0, PRL_FHP_AVG_DEFERRED = 1, PRL_FHP_AVG_CATCH_UP = 2 };
 struct PrlFhpParams {
     int32_t n_boards, R;
     int32_t np;                 // elements per board column = PRL_FHP_NP
@@ -195,6 +196,10 @@ struct PrlFhpParams {
                                 // float64 with the reference's weights, rounded on the store; `avg` is not touched by the board pass then
     int32_t avg_mode;           // 0: no update (before the delay), 1: avg = strategy, 2: avg = m_old * avg + m_new * strategy
     double m_old, m_new;        // CFRPlus.py:65-87 weights (float64)
+    // paired CFR+ average updates (prl_solver_iterations; prl_fhp_pass.inc, FhpCtxT): PRL_FHP_AVG_DEFERRED -- this iteration's update passes leave the
+    // board average alone; PRL_FHP_AVG_CATCH_UP -- they first apply the previous iteration's step with its weights below, then their own
+    int32_t avg_pair;
+    double m_old_prev, m_new_prev;
     // Vanilla / Linear CFR: the reach-weighted average of seat q needs q's NEW reach, known only after the trunk update that
     // follows q's pass -- so it rides on the next pass that walks q's reach (phase B for seat q): bit q of avgsum_mask
     float* avg_sum;             // board region: node.data["avg_strat_sum"] (VanillaCFR.py:40-55, LinearCFR.py:41-57)

@@ -10,7 +10,9 @@
 //     reach / ev / regrets of the current DFS path live in VGPRs;
 //   * HBM traffic per board and pass: 14 regret columns + ~15 KB of showdown plan in (prefetched into LDS by LDS-DMA while
 //     the previous board is walked), the updated seat's 7 regret columns and float64 average columns read-modify-written,
-//     one row of 1-4 root vectors out -- nothing else;
+//     one row of 1-4 root vectors out -- nothing else. CFR+ inside one prl_solver_iterations call: the float64 average columns are
+//     touched by every SECOND iteration only -- the pass kinds "deferred" (no average traffic at all) and "catch-up" (the previous
+//     iteration's step and its own, both in registers), prl_fhp_pass.inc FhpCtxT kinds 5 / 6, PrlFhpParams::avg_pair;
 //   * the only cross-hand step, terminal equity, goes through LDS in the rank-sorted domain: six-op DPP wave scans over
 //     the sorted range and over the 47 per-card blocker lists, the canonical order of DESIGN.md, so the result is
 //     bit-identical to engine G (prl_tree_kernels.hip) and to the CPU oracle;

@@ -241,23 +241,37 @@ PRL_DEV PRL_INLINE FhpLds fhp_lds() {
 // no Vanilla / Linear sum riding on the walk): the wave-uniform run-time switches below are compile-time constants, which removes
 // their scalar tests, the dead sides of every select and the SGPRs that held them (a clamp r > 0 ? r : 0 on regrets that CFR+
 // already stores clamped costs three instructions per regret otherwise).
-template <int STEADY>  // 0 generic; 1 CFR+, 2 Linear CFR, 3 vanilla CFR in their steady state (prl_fhp_steady_kind)
+//
+// PAIRED AVERAGE UPDATES (PrlFhpParams::avg_pair). The CFR+ average is a scalar-weighted recurrence, a_t = m_old_t * a_(t-1) + m_new_t * s_t, and the
+// strategy s_t that enters it -- regret matching of the regrets iteration t stores -- is recomputed by the pass of iteration t + 1 anyway (it plays
+// it). So of a pair (t, t + 1) inside one prl_solver_iterations call, t leaves the board average alone (DEFERRED: no old-average loads, no new-strategy
+// divisions where nothing else needs them, no average stores) and t + 1 applies both steps in registers (CATCH-UP: the node's old strategy s[i][k],
+// already there for the EV, with iteration t's weights, then its own step): the same operations in the same order with the same roundings, one HBM
+// round trip of the float64 columns instead of two. STEADY 5 / 6 are the two as compile-time kinds; the generic instantiation asks at run time.
+constexpr bool fhp_steady_plus(int steady) { return steady == 1 || steady == 4 || steady == 5 || steady == 6; }
+template <int STEADY>  // 0 generic; 1 CFR+, 2 Linear CFR, 3 vanilla CFR in their steady state; 4 CFR+ with the float32 average; 5 / 6 CFR+ deferred / catch-up
 struct FhpCtxT {
     // Where the own float32 columns of the first batch are requested from HBM (opponent-only prefetch). At the board start wherever phase B has no
     // run-time branches around vector-memory operations (the CFR+ steady state; strategies that are not regret-matched): three phases of cover and an
     // empty memory queue. After phase B otherwise: the pending Vanilla / Linear average update of the opponent's walk sits behind a run-time test, the
     // compiler's wait counts at the joins are conservative, and a load in flight there is waited for in the middle of phase B (measured: the
     // best-response pass 3.06 -> 2.77 ms when its walk lost those joins; the CFR+ steady passes +4 % with the requests behind the prefetch issue).
-    static constexpr bool own_after_b(int src_opp) { return src_opp == PRL_SRC_REGRET && !(STEADY == 1 || STEADY == 4); }
+    static constexpr bool own_after_b(int src_opp) { return src_opp == PRL_SRC_REGRET && !fhp_steady_plus(STEADY); }
     PRL_DEV PRL_INLINE int variant() const {
-        if constexpr (STEADY == 1 || STEADY == 4) return PRL_CFR_PLUS;
+        if constexpr (fhp_steady_plus(STEADY)) return PRL_CFR_PLUS;
         else if constexpr (STEADY == 2) return PRL_CFR_LINEAR;
         else if constexpr (STEADY == 3) return PRL_CFR_VANILLA;
         else return variant_;
     }
     PRL_DEV PRL_INLINE bool first_iteration() const { if constexpr (STEADY != 0) return false; else return iter == 0; }
-    PRL_DEV PRL_INLINE int avg_mode() const { if constexpr (STEADY == 1 || STEADY == 4) return 2; else if constexpr (STEADY >= 2) return 0; else return prm->avg_mode; }
-    PRL_DEV PRL_INLINE int avgsum_mask() const { if constexpr (STEADY == 1 || STEADY == 4) return 0; else return prm->avgsum_mask; }
+    PRL_DEV PRL_INLINE int avg_mode() const {
+        if constexpr (STEADY == 1 || STEADY == 4 || STEADY == 6) return 2;
+        else if constexpr (STEADY != 0) return 0;
+        else return prm->avg_pair == PRL_FHP_AVG_DEFERRED ? 0 : prm->avg_mode;
+    }
+    // the blend first applies the previous iteration's step, which that iteration left out (avg_mode() == 2 whenever this holds)
+    PRL_DEV PRL_INLINE bool avg_catch_up() const { if constexpr (STEADY == 6) return true; else if constexpr (STEADY != 0) return false; else return prm->avg_pair == PRL_FHP_AVG_CATCH_UP; }
+    PRL_DEV PRL_INLINE int avgsum_mask() const { if constexpr (fhp_steady_plus(STEADY)) return 0; else return prm->avgsum_mask; }
     // the running average is stored as float32 (opt-in): STEADY 4 = the CFR+ steady state with it; the generic instantiation asks at run time
     PRL_DEV PRL_INLINE bool avg32() const { if constexpr (STEADY == 4) return true; else if constexpr (STEADY != 0) return false; else return prm->avg32 != nullptr; }
     FhpLds L;
@@ -729,7 +743,11 @@ struct FhpUp {
                             for (int k = 0; k < FHP_SLOTS; ++k) {
                                 const float sn = qn[i][k];
                                 if (KEEP) R.rg[col0 + i][k] = sn;
-                                an[k] = c.avg_mode() == 2 ? c.prm->m_old * c.av_old[col0 + i][k] + c.prm->m_new * (double)sn : (double)sn;
+                                double ao = c.av_old[col0 + i][k];
+                                if constexpr (SRC == PRL_SRC_REGRET) {  // (the step iteration t - 1 deferred: its strategy is the one this node just played)
+                                    if (c.avg_catch_up()) ao = c.prm->m_old_prev * ao + c.prm->m_new_prev * (double)s[i][k];
+                                }
+                                an[k] = c.avg_mode() == 2 ? c.prm->m_old * ao + c.prm->m_new * (double)sn : (double)sn;
                             }
                             if (c.avg_mode()) {
                                 if (c.avg32()) {
@@ -1132,7 +1150,8 @@ int launch_pass(const PrlFhpParams& prm, int mode, int src0, int src1, void* str
     const int key = mode * 100 + src0 * 10 + src1;
     // steady-state kinds (FhpCtxT): CFR+ blending its running average, or Linear / vanilla CFR, after the first iteration
     const int steady = prm.no_steady || prm.iter == 0 ? 0
-                       : (prm.variant == PRL_CFR_PLUS && prm.avg_mode == 2 && prm.avgsum_mask == 0) ? (prm.avg32 ? 4 : 1)
+                       : (prm.variant == PRL_CFR_PLUS && prm.avg_mode == 2 && prm.avgsum_mask == 0)
+                           ? (prm.avg32 ? 4 : prm.avg_pair == PRL_FHP_AVG_DEFERRED ? 5 : prm.avg_pair == PRL_FHP_AVG_CATCH_UP ? 6 : 1)
                        : (prm.variant == PRL_CFR_LINEAR && prm.avg_mode == 0) ? 2
                        : (prm.variant == PRL_CFR_VANILLA && prm.avg_mode == 0) ? 3 : 0;
     switch (key) {
@@ -1145,6 +1164,8 @@ int launch_pass(const PrlFhpParams& prm, int mode, int src0, int src1, void* str
         case PRL_FHP_UPDATE0_BR * 100 + PRL_SRC_REGRET * 10 + PRL_SRC_REGRET:
             if (steady == 1) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 1>(prm, grid, stream);
             else if (steady == 4) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 4>(prm, grid, stream);
+            else if (steady == 5) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 5>(prm, grid, stream);
+            else if (steady == 6) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 6>(prm, grid, stream);
             else if (steady == 2) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 2>(prm, grid, stream);
             else if (steady == 3) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 3>(prm, grid, stream);
             else fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET>(prm, grid, stream);
@@ -1152,6 +1173,8 @@ int launch_pass(const PrlFhpParams& prm, int mode, int src0, int src1, void* str
         case PRL_FHP_UPDATE1_EVAL1 * 100 + PRL_SRC_REGRET * 10 + PRL_SRC_REGRET:
             if (steady == 1) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 1>(prm, grid, stream);
             else if (steady == 4) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 4>(prm, grid, stream);
+            else if (steady == 5) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 5>(prm, grid, stream);
+            else if (steady == 6) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 6>(prm, grid, stream);
             else if (steady == 2) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 2>(prm, grid, stream);
             else if (steady == 3) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 3>(prm, grid, stream);
             else fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET>(prm, grid, stream);

@@ -95,11 +95,14 @@ struct prl_solver {
     int src[2] = {PRL_SRC_UNIFORM64, PRL_SRC_UNIFORM64};
     bool board_avg_f64 = false;
     bool board_avg_stale = false;  // FUSED Vanilla / Linear: avg_sum moved on, the avg columns of the boards have not been recomputed yet
+    bool avg_deferred = false;     // FUSED CFR+, paired average updates (prl_solver_iterations): the board average lacks the last iteration's step, which
+                                   // the next iteration of the same call applies; set across a return only if an iteration failed in between
     float* d_regret = nullptr;  // [full_cols][R]
     double* d_avg = nullptr;    // [full_cols][R] (avg_f32: the trunk's columns only)
     float* d_avg32 = nullptr;   // opt-in (PRL_SOLVER_AVG_F32): the board columns' running average stored as float32, [full_cols][R]
     bool avg_f32 = false;
     long long n_exchanges = 0;  // all-gathers done so far (PRL_SF_EXCHANGES)
+    long long n_avg_pairs = 0;  // paired CFR+ average updates completed so far (PRL_SF_AVG_PAIRS)
     void* rccl_comm = nullptr;  // sharded solve with the library's own exchange (prl_solver_create_sharded_rccl): ncclComm_t
     // ---- per-street fused engine (prl_st.h): `fused` with the board pass replaced by a sweep over the streets ----
     bool streets = false;
@@ -436,6 +439,7 @@ int do_update_reach(prl_solver* s, const PrlDevState& st) {
 
 // FUSED Vanilla / Linear: the board pass maintains avg_sum only; readers of the average call this first
 static int ensure_board_avg(prl_solver* s) {
+    if (s->avg_deferred) { prl_set_error("the board average is incomplete: an iteration failed between the two halves of a paired average update; reset() or load_state()"); return PRL_ERR_STATE; }
     if (!s->fused || !s->board_avg_stale) return PRL_OK;
     if (s->streets) {
         for (int lv = 0; lv < s->st.n_groups; ++lv) {
@@ -1699,6 +1703,7 @@ int32_t prl_solver_load_state(prl_solver_t* s, const void* in, uint64_t bytes) {
     s->iter = h.iter; s->src[0] = h.src0; s->src[1] = h.src1; s->board_avg_f64 = h.board_avg_f64 != 0; s->board_avg_stale = false;
     s->user_strategy_f64 = -1; s->expl_pending = false; s->have_half = false; s->avg_pending[0] = s->avg_pending[1] = -1;
     s->ev_valid = false;
+    s->avg_deferred = false;
     for (double& a : s->blk_avg) a = 0.;  // the blocked hands' average: a function of the iteration count alone
     for (int it = 0; it < s->iter; ++it) {
         int mode; double m_old, m_new;
@@ -1799,6 +1804,7 @@ int32_t prl_solver_reset(prl_solver_t* s) {
     PRL_HIP_TRY(hipMemsetAsync(s->S.avg_f64, 0, (size_t)s->T.n_nodes, s->stream));
     if (s->S.avg_sum) PRL_HIP_TRY(hipMemsetAsync(s->S.avg_sum, 0, nc * sizeof(float), s->stream));
     s->board_avg_f64 = false; s->board_avg_stale = false;
+    s->avg_deferred = false;
     TRY(prl_solver_fill_uniform(s));
     TRY(ensure_ev(s));
     return record_expl(s);
@@ -1896,7 +1902,10 @@ int32_t prl_solver_compute_ev(prl_solver_t* s) {  // PublicTree.compute_ev (Publ
 // closed the previous iteration; that pass is reused (identical values), so an iteration costs two EV passes, not three.
 // FUSED: every half-iteration is one board pass that computes the EVs and updates that seat's regrets in place, then the
 // trunk is updated with the summed chance-node values; a third (best-response) pass yields the exploitability.
-static int iteration_core(prl_solver* s, bool closing_eval) {
+// avg_pair (prl_fhp.h: PRL_FHP_AVG_*, chosen by prl_solver_iterations): the board passes of this iteration leave the boards' CFR+ average alone
+// (DEFERRED), or apply the previous iteration's step before their own (CATCH_UP). Everything else -- the trunk's average, the blocked hands'
+// recurrence, the exploitability bookkeeping -- is per iteration as ever.
+static int iteration_core(prl_solver* s, bool closing_eval, int avg_pair = PRL_FHP_AVG_NORMAL) {
     if (s->fused && s->user_strategy_f64 >= 0) { prl_set_error("call reset() / fill_uniform() before iterating after set_strategy()"); return PRL_ERR_STATE; }
     int mode = 0;
     double m_old = 0., m_new = 0.;
@@ -1904,6 +1913,14 @@ static int iteration_core(prl_solver* s, bool closing_eval) {
     s->fp.avg_mode = mode;
     s->fp.m_old = m_old;
     s->fp.m_new = m_new;
+    s->fp.avg_pair = avg_pair;
+    s->fp.m_old_prev = s->fp.m_new_prev = 0.;
+    if (avg_pair == PRL_FHP_AVG_CATCH_UP) {
+        int mode_prev = 0;
+        cfr_plus_weights(s, s->iter - 1, &mode_prev, &s->fp.m_old_prev, &s->fp.m_new_prev);
+        if (mode_prev != 2 || mode != 2) { prl_set_error("paired average update outside the blending iterations"); return PRL_ERR_STATE; }
+    }
+    if (avg_pair == PRL_FHP_AVG_DEFERRED) s->avg_deferred = true;  // until the catch-up iteration's passes are launched
     for (int p = 0; p < 2; ++p) {
         bool second_half = false;
         if (s->fused) {
@@ -1934,6 +1951,8 @@ static int iteration_core(prl_solver* s, bool closing_eval) {
         if (second_half) s->have_half = true;  // d_half: seat 1's value / best response under the updated strategies
     }
     s->fp.avg_mode = 0;
+    s->fp.avg_pair = PRL_FHP_AVG_NORMAL;
+    if (avg_pair == PRL_FHP_AVG_CATCH_UP) { s->avg_deferred = false; ++s->n_avg_pairs; }
     if (s->sorted) blocked_avg_step(s, mode, m_old, m_new);
     s->iter += 1;
     if (s->fused && !closing_eval) {
@@ -2097,7 +2116,24 @@ int32_t prl_solver_iterations(prl_solver_t* s, int32_t n) {
         if (rc != PRL_ERR_UNSUPPORTED) return rc;
     }
 #endif
-    for (int i = 0; i < n; ++i) TRY(iteration_core(s, i == n - 1));
+    if (s->avg_deferred) { prl_set_error("an iteration failed between the two halves of a paired average update; reset() or load_state()"); return PRL_ERR_STATE; }
+    // PAIRED AVERAGE UPDATES (single-deal fused engine, CFR+, float64 average): the strategy that iteration t blends into the board average is the
+    // one iteration t + 1 plays, so t leaves the float64 columns alone and t + 1 applies both steps in registers (prl_fhp_pass.inc, FhpCtxT) -- one
+    // HBM round trip of the average per pair. Pairs never span calls: nothing is pending when this returns, a leftover last iteration runs the
+    // plain pass. PRL_FHP_NO_AVG_PAIR (read at every call, so that one solver object can be timed both ways) turns it off.
+    const bool may_pair = s->fused && !s->streets && s->variant == PRL_CFR_PLUS && !s->avg_f32 && !getenv("PRL_FHP_NO_AVG_PAIR");
+    bool deferred = false;
+    for (int i = 0; i < n; ++i) {
+        int avg_pair = PRL_FHP_AVG_NORMAL;
+        if (deferred) avg_pair = PRL_FHP_AVG_CATCH_UP;
+        else if (may_pair && i + 1 < n && s->src[0] == PRL_SRC_REGRET && s->src[1] == PRL_SRC_REGRET && s->user_strategy_f64 < 0) {
+            int mode; double m_old, m_new;
+            cfr_plus_weights(s, s->iter, &mode, &m_old, &m_new);
+            if (mode == 2) avg_pair = PRL_FHP_AVG_DEFERRED;  // (mode 2 holds for every later iteration)
+        }
+        TRY(iteration_core(s, i == n - 1, avg_pair));
+        deferred = avg_pair == PRL_FHP_AVG_DEFERRED;
+    }
     return PRL_OK;
 }
 
@@ -2454,6 +2490,7 @@ int32_t prl_solver_get(prl_solver_t* s, int32_t field, void* out) {
         case PRL_SF_ENGINE: *(int32_t*)out = s->fused ? PRL_ENGINE_FUSED : PRL_ENGINE_LEVELS; return PRL_OK;
         case PRL_SF_GRAPH_REPLAY: *(int32_t*)out = s->levels_graph_exec != nullptr; return PRL_OK;
         case PRL_SF_EXCHANGES: *(int64_t*)out = (int64_t)s->n_exchanges; return PRL_OK;
+        case PRL_SF_AVG_PAIRS: *(int64_t*)out = (int64_t)s->n_avg_pairs; return PRL_OK;
         case PRL_SF_VMM_RANGES: {
             int64_t bytes = 0;
 #if !defined(PRL_EMU)

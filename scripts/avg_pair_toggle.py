@@ -1,0 +1,45 @@
+"""A/B of the paired CFR+ average updates on ONE solver object (same memory, same stream): PRL_FHP_NO_AVG_PAIR is read at every
+prl_solver_iterations call, so time_iterations_ex(20) is called alternately with the switch set and unset. One object repeats to ~0.1 %, while
+different objects differ by up to 15 % from physical placement ("Spread") -- which is why the comparison stays on one.
+Prints the board-pass kernel ms per iteration of every repeat and a JSON summary (last line).
+Usage: python scripts/avg_pair_toggle.py [rounds] [boards] [iterations per timing]"""
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bench  # noqa: E402
+from pokerrl_amd import _native  # noqa: E402
+
+rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 6
+n_boards = int(sys.argv[2]) if len(sys.argv) > 2 else 262144
+n_it = int(sys.argv[3]) if len(sys.argv) > 3 else 20
+_native.require_device()
+tree = bench.fhp_tree(bench.seeded_boards(n_boards, 0), None)
+s = _native.NativeSolver(tree, "plus", 0, engine="fused")
+s.iterations(4)
+os.environ["PRL_FHP_NO_AVG_PAIR"] = "1"
+s.time_iterations_ex(n_it)  # warm both paths' kernels
+del os.environ["PRL_FHP_NO_AVG_PAIR"]
+s.time_iterations_ex(n_it)
+res = {"unpaired": {"kernel_ms": [], "device_ms": []}, "paired": {"kernel_ms": [], "device_ms": []}}
+for r in range(rounds):
+    for name in ("unpaired", "paired"):
+        if name == "unpaired":
+            os.environ["PRL_FHP_NO_AVG_PAIR"] = "1"
+        else:
+            os.environ.pop("PRL_FHP_NO_AVG_PAIR", None)
+        pairs0 = int(s.get("avg_pairs")[0])
+        dev_ms, pass_ms, n_pass = s.time_iterations_ex(n_it)
+        assert int(s.get("avg_pairs")[0]) - pairs0 == (n_it // 2 if name == "paired" else 0)
+        res[name]["kernel_ms"].append(pass_ms / n_it)
+        res[name]["device_ms"].append(dev_ms / n_it)
+        print("round %d %-8s board-pass kernels %.4f ms / iteration, device %.4f ms / iteration (%d launches)" % (r, name, pass_ms / n_it, dev_ms / n_it, n_pass), flush=True)
+os.environ.pop("PRL_FHP_NO_AVG_PAIR", None)
+out = {"boards": n_boards, "iterations_per_timing": n_it, "rounds": rounds, "iterations_done": s.iter}
+for name, d in res.items():
+    for k, v in d.items():
+        out["%s_%s" % (name, k)] = {"mean": sum(v) / len(v), "min": min(v), "max": max(v), "all": v}
+out["kernel_ms_ratio_paired_over_unpaired"] = out["paired_kernel_ms"]["mean"] / out["unpaired_kernel_ms"]["mean"]
+out["device_ms_ratio_paired_over_unpaired"] = out["paired_device_ms"]["mean"] / out["unpaired_device_ms"]["mean"]
+print(json.dumps(out))
