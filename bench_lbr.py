@@ -144,6 +144,10 @@ def main():
                       "hand_evals_per_s_rank0": sum(s["range_board_equities"] for s in stats) * 1326 / dev_s,
                       "lbr_winnings_mbb_per_g": mean, "lbr_winnings_per_agent_seat_mbb_per_g": [r[0] for r in res], "conf95_per_seat": [r[1] for r in res],
                       "whole_game_solve": solve}}
+    if args.lbr_from_the_start:  # the request / replay rounds: what the wall clock holds beside the timed kernels (the requests' equities, the replays)
+        out["config"]["wall_s"] = dt
+        for k in ("equity_rounds", "equity_requests", "equity_host_calls", "equity_ms"):
+            out["config"][k] = sum(s[k] for s in stats) if all(k in s for s in stats) else None
     # The batch kernel keeps a hand's whole state in LDS / registers: HBM moves the decks in and the winnings out (bytes per hand in the
     # tens), and nothing in it is a contraction: neither the HBM nor the MFMA roofline says anything about it. It is bound by VECTOR
     # INSTRUCTION ISSUE, integer and float32 alike, and the model counts what the kernel executes for the dominant step, the (range, board)

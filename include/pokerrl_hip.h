@@ -501,9 +501,19 @@ int32_t prl_solver_get_cols(prl_solver_t* solver, int32_t field, int64_t col_beg
 /*    ranges: [n_q][R] candidate agent ranges (the current one, and the one after "agent does not fold" per raise);    */
 /*    out_wp[n_q]: P(LBR wins the check-down) per range. Any number of board cards to come: hold'em before the flop     */
 /*    enumerates all C(50, 5) = 2 118 760 run-outs (LocalLBRWorker.py:388-425), about a second per decision.           */
+/*    prl_lbr_checkdown_equity answers ONE decision per call (the host worker's call); independent decisions go         */
+/*    through prl_lbr_checkdown_equity_batch, which shares the launches and runs their float32 chains side by side.     */
 /* ---------------------------------------------------------------------------------------------------------------- */
 int32_t prl_lbr_checkdown_equity(const PrlRules* rules, const int8_t* board_dealt, int32_t n_dealt, const int8_t* lbr_hand,
                                  const float* ranges, int32_t n_q, float* out_wp);
+/* n_req independent decisions in one call; request i equals prl_lbr_checkdown_equity(rules, boards_dealt + 5*i, n_dealt[i],
+ * lbr_hands + n_hole*i, ranges + i*q_stride*R, n_q[i], out_wp + i*q_stride) bit for bit. Requests may differ in n_dealt and n_q (1 <= n_q[i] <= q_stride);
+ * slots of out_wp at or beyond n_q[i] keep what the caller put there. The (range, board) equities of the requests pass through one device buffer in
+ * chunks of at most PRL_LBR_EQ_BATCH_MB megabytes (environment, read at every call; default 8192; a request larger than that is a chunk of its own). The
+ * number of host synchronisations does not depend on n_req. Same argument checks and error codes as the single call. */
+int32_t prl_lbr_checkdown_equity_batch(const PrlRules* rules, int32_t n_req, const int8_t* boards_dealt /*[n_req][5]*/, const int32_t* n_dealt,
+                                       const int8_t* lbr_hands /*[n_req][n_hole]*/, const float* ranges /*[n_req][q_stride][R]*/,
+                                       const int32_t* n_q, int32_t q_stride, float* out_wp /*[n_req][q_stride]*/);
 
 /* Device-resident batched LBR (BASELINE config 5): n_envs hands of LocalLBRWorker.run (LocalLBRWorker.py:61-308) against a
  * synthetic tabular agent, each played start to finish by one workgroup: betting engine (PokerEnv._step), dealing, the
@@ -517,12 +527,18 @@ int32_t prl_lbr_checkdown_equity(const PrlRules* rules, const int8_t* board_deal
  *   LBR decisions with at most two board cards to come are evaluated inside the kernel. Decisions with more -- hold'em BEFORE THE FLOP, i.e.
  *   lbr_check_to_round = None, the reference's default (LBRArgs.py:18; enumeration LocalLBRWorker.py:388-425) -- need C(50, 5) boards per candidate
  *   range, which are a function of the public history and LBR's hand only: they are cached per (history key, LBR hand) in HBM. A hand that misses
- *   files a request and stops; the call computes the requested equities with prl_lbr_checkdown_equity (the host worker's own call at that decision),
+ *   files a request and stops; the call computes a round's requested equities where they lie, in one batch (the core of
+ *   prl_lbr_checkdown_equity_batch: request for request the host worker's own prl_lbr_checkdown_equity call at that decision, bit for bit),
  *   fills the cache and plays the stopped hands again from the start (counter-based decks and draws: a replay reaches the same decision with the
  *   same ranges) -- rounds of launches until no hand waits; the counters include the replays. Same per-hand winnings as the host worker. */
 int32_t prl_lbr_batch_run(const PrlGame* lbr_game, const PrlGame* agent_game, const PrlRules* rules, int32_t n_envs, int32_t agent_seat,
                           int32_t check_to_round, int32_t agent_kind, uint32_t agent_seed, uint32_t episode_base, double reward_scalar,
                           double ev_normalizer, const int8_t* cards, float* out_winnings, uint64_t* out_stats4, float* out_device_ms);
+/* The calling thread's last prl_lbr_batch_run / prl_lbr_batch_run_table: out8 = request / replay rounds, equity requests answered, requests answered
+ * by a per-request host call (0: a round's requests are answered in one batch on the device), chunks the equity buffer was filled in, the device
+ * time of the requests' equities in ms (HIP events; not part of out_device_ms), keys in the equity cache at the end, 0, 0. All 0 for a run whose
+ * look-aheads never have more than two cards to come. */
+int32_t prl_lbr_batch_last_info(double* out8);
 
 /* Batched head-to-head (PokerRL/eval/head_to_head/LocalHead2HeadMaster.py:82-126 on the batched env): n_envs
  * hands between two of the library's synthetic agents, one GPU lane per hand (betting engine, the acting agent's row of its

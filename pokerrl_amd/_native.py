@@ -185,6 +185,10 @@ def _bind_solver(L):
     L.prl_solver_time_evaluations.restype = i32
     L.prl_lbr_checkdown_equity.argtypes = [ctypes.POINTER(PrlRules), vp, i32, vp, vp, i32, vp]
     L.prl_lbr_checkdown_equity.restype = i32
+    L.prl_lbr_checkdown_equity_batch.argtypes = [ctypes.POINTER(PrlRules), i32, vp, vp, vp, vp, vp, i32, vp]
+    L.prl_lbr_checkdown_equity_batch.restype = i32
+    L.prl_lbr_batch_last_info.argtypes = [vp]
+    L.prl_lbr_batch_last_info.restype = i32
     L.prl_lbr_batch_run.argtypes = [ctypes.POINTER(PrlGame), ctypes.POINTER(PrlGame), ctypes.POINTER(PrlRules), i32, i32, i32, i32,
                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]
     L.prl_lbr_batch_run.restype = i32

@@ -8,6 +8,9 @@
 #if defined(PRL_EMU)
 #include "prl_emu.h"
 #define PRL_LAUNCH_BOUNDS(n)
+// grid_x x grid_y workgroups (the emulator's launch2 runs them one after another)
+#define PRL_LAUNCH_XY(kernel, grid_x, grid_y, block, smem, stream, ...) \
+    prl_emu::launch2([=]() { kernel(__VA_ARGS__); }, (unsigned)(grid_x), (unsigned)(grid_y), (unsigned)(block), (size_t)(smem))
 inline void prl_atomic_add_u64(unsigned long long* p, unsigned long long v) { *p += v; }  // the emulator runs one fiber at a time
 inline void prl_lds_add_i(int* p, int v) { *p += v; }
 inline void prl_lds_min_u(unsigned* p, unsigned v) { if (v < *p) *p = v; }
@@ -23,6 +26,9 @@ inline unsigned long long prl_atomic_cas_u64(unsigned long long* p, unsigned lon
 // functions written for a grid-stride launch cover all of their items inside the one workgroup
 #define PRL_LAUNCH_Y(kernel, grid_y, block, smem, stream, ...) \
     hipLaunchKernelGGL(kernel, dim3(1u, (unsigned)(grid_y)), dim3((unsigned)(block)), (size_t)(smem), (hipStream_t)(stream), __VA_ARGS__)
+// grid_x x grid_y workgroups: prl_bid_y() picks the work item, prl_bid() / prl_nblocks() stride over its elements
+#define PRL_LAUNCH_XY(kernel, grid_x, grid_y, block, smem, stream, ...) \
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(grid_x), (unsigned)(grid_y)), dim3((unsigned)(block)), (size_t)(smem), (hipStream_t)(stream), __VA_ARGS__)
 #define PRL_LAUNCH_BOUNDS(n) __launch_bounds__(n)
 PRL_DEV PRL_INLINE void prl_atomic_add_u64(unsigned long long* p, unsigned long long v) { atomicAdd(p, v); }
 PRL_DEV PRL_INLINE void prl_lds_add_i(int* p, int v) { atomicAdd(p, v); }  // integer add on an LDS word (order-free)

@@ -26,6 +26,7 @@
 #include "prl_env.h"
 #include "prl_host.h"
 #include "prl_lbr.h"
+#include "prl_lbr_equity_batch.h"
 #include "prl_policy.h"
 #include "prl_rt.h"
 
@@ -64,9 +65,9 @@ struct PrlLbrBatchParams {
     // PRE builds: LBR decisions with more than two board cards to come (hold'em before the flop: lbr_check_to_round = None, the reference's default,
     // LBRArgs.py:18). Such a check-down equity is C(50, 5) = 2 118 760 boards per candidate range -- no hand can afford it, and no hand has to: the
     // candidate ranges are a function of the PUBLIC history and of LBR's hand only, so the equities are cached per (history key, LBR hand) in HBM. A
-    // hand that misses files a request (its candidate ranges) and stops; the host computes the requested equities with the stand-alone kernel
-    // (prl_lbr_checkdown_equity: what the host worker calls at the same decision), puts them into the cache and plays the stopped hands AGAIN from
-    // the start -- decks and agent draws are counter-based, so a replay reaches the same decision with the same ranges, and hits.
+    // hand that misses files a request (its candidate ranges) and stops; the round's requests are answered in one batch where they lie
+    // (prl_lbr_equity_batch.hip: request for request what prl_lbr_checkdown_equity, the host worker's call at the same decision, returns), the host
+    // puts the results into the cache and plays the stopped hands AGAIN from the start -- decks and agent draws are counter-based, so a replay reaches the same decision with the same ranges, and hits.
     const int32_t* env_list;      // [n_envs] the hands this launch plays (nullptr: 0 .. n_envs - 1)
     int32_t* status;              // [all hands] 1 = stopped at a missing equity
     const unsigned long long* pf_keys;  // [pf_mask + 1] cache: key of (history, LBR hand), 0 = empty
@@ -1175,6 +1176,16 @@ static int lbrb_check_table(int kind, const PrlPolicyTable* T, const PrlGame* ag
     return PRL_OK;
 }
 
+// the calling thread's last batched run (prl_lbr_batch_last_info): rounds, equity requests answered, requests answered by a per-request host call
+// (none since the requests are answered where they lie), chunks of the equity core, the core's device time in ms, cached keys, 0, 0
+static thread_local double g_lbrb_info[8];
+
+extern "C" int32_t prl_lbr_batch_last_info(double* out8) {
+    if (!out8) { prl_set_error("bad argument"); return PRL_ERR_ARG; }
+    memcpy(out8, g_lbrb_info, sizeof(g_lbrb_info));
+    return PRL_OK;
+}
+
 static int32_t lbr_batch_run_impl(const PrlGame* lbr_game, const PrlGame* agent_game, const PrlRules* rules, int32_t n_envs, int32_t agent_seat,
                                   int32_t check_to_round, int32_t agent_kind, uint32_t agent_seed, uint32_t episode_base, double reward_scalar,
                                   double ev_normalizer, const int8_t* cards, float* out_winnings, uint64_t* out_stats4, float* out_device_ms, const PrlPolicyTable* table) {
@@ -1212,19 +1223,26 @@ static int32_t lbr_batch_run_impl(const PrlGame* lbr_game, const PrlGame* agent_
     const size_t smem = lbrb_smem_bytes(R);
     int8_t* d_cards = nullptr; float* d_win = nullptr; unsigned long long* d_stats = nullptr; float* d_eq = nullptr;
     // PRE: the cache, the requests of a round, the hands of a round
-    const int max_req = 1024;
-    const uint32_t req_cap = 4096;
+    // PRL_LBRB_MAX_REQ: requests accepted per round; PRL_LBRB_PF_CAP: the cache's first capacity (tests: small games walk the overflow and growth paths)
+    int max_req = 1024;
+    uint32_t req_cap = 4096, pf_cap = 4096;
+    if (const char* ev = getenv("PRL_LBRB_MAX_REQ")) { const int v = atoi(ev); if (v > 0) max_req = v < 16384 ? v : 16384; }
+    if (const char* ev = getenv("PRL_LBRB_PF_CAP")) { const int v = atoi(ev); if (v > 0) for (pf_cap = 2; pf_cap < (uint32_t)v && pf_cap < (1u << 30); pf_cap *= 2) {} }
+    for (req_cap = 8; req_cap < 4u * (uint32_t)max_req; req_cap *= 2) {}  // the request key table: at most a quarter full
     int32_t *d_list = nullptr, *d_status = nullptr, *d_n_req = nullptr, *d_req_meta = nullptr;
     unsigned long long *d_pf_keys = nullptr, *d_req_keys = nullptr, *d_req_key_of = nullptr;
-    float *d_pf_wp = nullptr, *d_req_ranges = nullptr;
+    float *d_pf_wp = nullptr, *d_req_ranges = nullptr, *d_req_wp = nullptr;
+    PrlLbrEqWork eq_work;  // the equity core's buffers: they live as long as the run
+    std::vector<float> req_wp;
     std::vector<unsigned long long> c_keys;
     std::vector<float> c_wp;
     uint32_t c_cap = 0, c_used = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float total_ms = 0.f;
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
+    float total_ms = 0.f, eq_ms = 0.f;
     int n_rounds = 0;
-    long long n_requests = 0;
+    long long n_requests = 0, n_chunks = 0;
     int rc = PRL_OK;
+    memset(g_lbrb_info, 0, sizeof(g_lbrb_info));
 #define LB_TRY(x) do { if ((x) != hipSuccess) { prl_set_error("HIP error in prl_lbr_batch_run"); rc = PRL_ERR_HIP; goto done; } } while (0)
     LB_TRY(hipMalloc((void**)&d_cards, (size_t)n_envs * P.n_deal));
     LB_TRY(hipMalloc((void**)&d_win, (size_t)n_envs * sizeof(float)));
@@ -1267,8 +1285,9 @@ static int32_t lbr_batch_run_impl(const PrlGame* lbr_game, const PrlGame* agent_
             // rounds: play the hands that are left; compute what they asked for; play the stopped ones again
             std::vector<int32_t> list((size_t)n_envs), status((size_t)n_envs), meta((size_t)max_req * 8);
             std::vector<unsigned long long> key_of((size_t)max_req);
-            std::vector<float> ranges;
             for (int i = 0; i < n_envs; ++i) list[i] = i;
+            LB_TRY(hipEventCreate(&e2));
+            LB_TRY(hipEventCreate(&e3));
             LB_TRY(hipMalloc((void**)&d_list, (size_t)n_envs * 4));
             LB_TRY(hipMalloc((void**)&d_status, (size_t)n_envs * 4));
             LB_TRY(hipMalloc((void**)&d_n_req, 4));
@@ -1276,7 +1295,9 @@ static int32_t lbr_batch_run_impl(const PrlGame* lbr_game, const PrlGame* agent_
             LB_TRY(hipMalloc((void**)&d_req_keys, (size_t)req_cap * 8));
             LB_TRY(hipMalloc((void**)&d_req_key_of, (size_t)max_req * 8));
             LB_TRY(hipMalloc((void**)&d_req_ranges, (size_t)max_req * LBRB_MAX_Q * R * sizeof(float)));
-            c_cap = 1u << 12;
+            LB_TRY(hipMalloc((void**)&d_req_wp, (size_t)max_req * LBRB_MAX_Q * sizeof(float)));
+            req_wp.resize((size_t)max_req * LBRB_MAX_Q);
+            c_cap = pf_cap;
             c_keys.assign(c_cap, 0ull);
             c_wp.assign((size_t)c_cap * LBRB_MAX_Q, 0.f);
             auto insert = [&](unsigned long long k, const float* wp) {
@@ -1332,27 +1353,28 @@ static int32_t lbr_batch_run_impl(const PrlGame* lbr_game, const PrlGame* agent_
                 if (n_req > 0) {
                     LB_TRY(hipMemcpy(meta.data(), d_req_meta, (size_t)n_req * 8 * 4, hipMemcpyDeviceToHost));
                     LB_TRY(hipMemcpy(key_of.data(), d_req_key_of, (size_t)n_req * 8, hipMemcpyDeviceToHost));
-                    ranges.resize((size_t)n_req * LBRB_MAX_Q * R);
-                    LB_TRY(hipMemcpy(ranges.data(), d_req_ranges, ranges.size() * sizeof(float), hipMemcpyDeviceToHost));
-                    for (int r = 0; r < n_req; ++r) {
-                        const int32_t* m = &meta[(size_t)r * 8];
-                        int c1 = m[0], c2 = 0;
-                        if (nh == 2) prl_hole_cards_2(m[0], rules->n_cards, &c1, &c2);
-                        const int8_t hand[2] = {(int8_t)c1, (int8_t)c2};
-                        int8_t board[5];
-                        for (int i = 0; i < 5; ++i) board[i] = (int8_t)(m[3 + i] < 0 ? 0 : m[3 + i]);
-                        float wp[LBRB_MAX_Q];
-                        memset(wp, 0, sizeof(wp));
-                        // the stand-alone equity of the host worker's own call at this decision (LocalLBRWorker._checkdown_equity -> prl_lbr_checkdown_equity)
-                        rc = prl_lbr_checkdown_equity(rules, board, m[2], hand, &ranges[(size_t)r * LBRB_MAX_Q * R], m[1], wp);
-                        if (rc != PRL_OK) goto done;
-                        insert(key_of[r], wp);
-                    }
+                    // the round's equities where the requests lie (prl_lbr_equity_batch.hip): request r = the host worker's own call at that decision
+                    // (LocalLBRWorker._checkdown_equity -> prl_lbr_checkdown_equity), bit for bit; n_req x LBRB_MAX_Q floats come back
+                    int chunks = 0;
+                    float ms_eq = 0.f;
+                    LB_TRY(hipMemset(d_req_wp, 0, (size_t)n_req * LBRB_MAX_Q * sizeof(float)));
+                    LB_TRY(hipEventRecord(e2, nullptr));
+                    rc = prl_lbr_equity_batch_device(rules, n_req, meta.data(), d_req_meta, d_req_ranges, LBRB_MAX_Q, d_req_wp, nullptr, &eq_work, &chunks);
+                    if (rc != PRL_OK) goto done;
+                    LB_TRY(hipEventRecord(e3, nullptr));
+                    LB_TRY(hipEventSynchronize(e3));
+                    LB_TRY(hipEventElapsedTime(&ms_eq, e2, e3));
+                    eq_ms += ms_eq;
+                    n_chunks += chunks;
+                    LB_TRY(hipMemcpy(req_wp.data(), d_req_wp, (size_t)n_req * LBRB_MAX_Q * sizeof(float), hipMemcpyDeviceToHost));
+                    for (int r = 0; r < n_req; ++r) insert(key_of[r], &req_wp[(size_t)r * LBRB_MAX_Q]);
                     n_requests += n_req;
                 }
                 list.swap(next);
             }
             if (getenv("PRL_LBRB_DEBUG")) fprintf(stderr, "lbrb: %d rounds, %lld equity requests, %u cached keys\n", n_rounds, n_requests, c_used);
+            g_lbrb_info[0] = n_rounds; g_lbrb_info[1] = (double)n_requests; g_lbrb_info[2] = 0.0; g_lbrb_info[3] = (double)n_chunks; g_lbrb_info[4] = eq_ms;
+            g_lbrb_info[5] = c_used;
         }
     }
     if (out_device_ms) *out_device_ms = total_ms;
@@ -1373,6 +1395,10 @@ static int32_t lbr_batch_run_impl(const PrlGame* lbr_game, const PrlGame* agent_
 done:
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
+    if (e2) (void)hipEventDestroy(e2);
+    if (e3) (void)hipEventDestroy(e3);
+    prl_lbr_eq_work_free(&eq_work);
+    (void)hipFree(d_req_wp);
     (void)hipFree(d_cards); (void)hipFree(d_win); (void)hipFree(d_stats); (void)hipFree(d_eq);
     (void)hipFree(d_list); (void)hipFree(d_status); (void)hipFree(d_n_req); (void)hipFree(d_req_meta); (void)hipFree(d_req_keys); (void)hipFree(d_req_key_of);
     (void)hipFree(d_req_ranges); (void)hipFree(d_pf_keys); (void)hipFree(d_pf_wp);

@@ -95,6 +95,13 @@ class BatchedLBR:
                          stats.ctypes.data_as(ctypes.c_void_p), ctypes.byref(ms)), L)
         self.last_stats = {"env_steps": int(stats[0]), "lbr_lookaheads": int(stats[1]), "range_board_equities": int(stats[2]),
                            "agent_actions": int(stats[3]), "device_ms": float(ms.value)}
+        # look-aheads with more than two cards to come (hold'em before the flop): the request / replay rounds and their equities, answered on the
+        # device a round at a time (equity_host_calls: requests that took a per-request host call -- none)
+        info = np.zeros(8, np.float64)
+        if hasattr(L, "prl_lbr_batch_last_info"):  # (A/B runs bind older builds of the library: no counters there)
+            _native.check(L.prl_lbr_batch_last_info(info.ctypes.data_as(ctypes.c_void_p)), L)
+            self.last_stats.update({"equity_rounds": int(info[0]), "equity_requests": int(info[1]), "equity_host_calls": int(info[2]),
+                                    "equity_chunks": int(info[3]), "equity_ms": float(info[4])})
         return out
 
     def run_sharded(self, agent_seat_id, n_hands_total, deck_seed=0, episode_base=0, group=None, device="cuda"):
