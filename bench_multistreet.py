@@ -5,10 +5,11 @@ fused engine (csrc/prl_st.h); --engine levels is the level-synchronous engine th
 tree, profiles/r04p_bench_multistreet.json).
 
     python bench_multistreet.py [--gpus N] [--flops F] [--turns T] [--rivers R] [--steps K] [--warmup W] [--engine auto|levels] [--no-cpu-baseline]
-                                [--game DiscretizedNLHoldem [--stack S]]
+                                [--game DiscretizedNLHoldem [--stack S] [--bets POT_ONLY|B_2]]
 
 --game DiscretizedNLHoldem (round 6): pot-sized raises with finite stacks -- the streets' subtrees differ in shape and all-in calls are dealt out as
-run-out chains ("mixed streets", csrc/prl_st.h).
+run-out chains ("mixed streets", csrc/prl_st.h). --bets B_2: pot and all-in raises, decisions with up to four actions; the per-street engine takes
+these trees up to 2500 chips (25 big blinds), deeper stacks run on the level-synchronous engine.
 
 N > 1 GPUs: the flops (first-deal outcomes) are sharded, F per GPU (weak scaling: N x F flops in all), the betting before the flop replicated,
 one all-gather of the first street's root rows per EV pass (inside the library over RCCL; `--gpus N` starts the ranks itself as bench.py does).
@@ -29,7 +30,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
-def pmc_traffic(game, flops, turns, rivers):
+def pmc_traffic(game, flops, turns, rivers, bets="POT_ONLY"):
     """HBM bytes per last-street action column and CFR+ iteration from profiles/multistreet_counters.json (written by scripts/gpu_r6_ms_traffic.sh: rocprofv3
     --pmc FETCH_SIZE / WRITE_SIZE in separate runs, FETCH_SIZE doubled per MI355X_MICROARCH.md) -- (bytes per column, source text), or (None, why). The
     LimitHoldem figure scales to other run-out counts of the same game (one shape per street); a mixed-streets tree only has its own measurement."""
@@ -39,7 +40,7 @@ def pmc_traffic(game, flops, turns, rivers):
             d = json.load(f)
     except (OSError, ValueError):
         return None, "profiles/multistreet_counters.json not found"
-    key = "%s_%dx%dx%d" % (game, flops, turns, rivers)
+    key = "%s_%dx%dx%d" % (game, flops, turns, rivers) + ("" if bets == "POT_ONLY" else "_" + bets)  # (another bet set is another tree)
     if key not in d and game == "LimitHoldem":
         key = next((k for k in d if k.startswith("LimitHoldem_")), key)
     if key not in d:
@@ -93,6 +94,8 @@ def main():
     ap.add_argument("--placement-candidates", type=int, default=3, help="one GPU: solver objects built and timed before the run, the fastest is kept (1 = no probe)")
     ap.add_argument("--game", default="LimitHoldem", choices=["LimitHoldem", "DiscretizedNLHoldem"], help="DiscretizedNLHoldem: pot-sized raises (bet_sets.POT_ONLY) -- mixed street "
                     "shapes and all-in run-out chains (csrc/prl_st.h MIXED STREETS)")
+    ap.add_argument("--bets", default="POT_ONLY", choices=["POT_ONLY", "B_2"], help="DiscretizedNLHoldem: the raise sizes (pokerrl_amd.game.bet_sets); B_2 = pot and all-in, "
+                    "street shapes with four-action decisions")
     ap.add_argument("--stack", type=int, default=None, help="chips per seat (default: 48 for LimitHoldem, 2500 for DiscretizedNLHoldem)")
     ap.add_argument("--max-raises", default=None, help="raises per betting round, e.g. 1,1,1,1 (smaller street subtrees: the CPU test-suite's emulator runs); default: the game's 4")
     args = ap.parse_args()
@@ -128,7 +131,7 @@ def main():
     game_cls = getattr(G, args.game)
     nl = args.game == "DiscretizedNLHoldem"
     stack = args.stack if args.stack is not None else (2500 if nl else 48)
-    bets = bet_sets.POT_ONLY if nl else None
+    bets = getattr(bet_sets, args.bets) if nl else None
     if args.max_raises:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         from helpers import env_args
@@ -207,14 +210,14 @@ def main():
     n_trunk = int(np.sum(rnd == int(rnd.min())))  # the betting before the first deal: replicated on every rank, counted once
     n_nodes_job = n_trunk + world * (tree.n_nodes - n_trunk)
     achieved = (bytes_last * args.steps / (pass_ms * 1e-3) if fused else bytes_iter * args.steps / (dev_ms * 1e-3)) / 1e9
-    per_col, traffic_src = pmc_traffic(args.game, args.flops, args.turns, args.rivers)
+    per_col, traffic_src = pmc_traffic(args.game, args.flops, args.turns, args.rivers, args.bets)
     out = {
         "metric": "CFR+ node-updates/sec on a multi-street %s public tree" % args.game, "value": n_nodes_job * args.steps / dt, "unit": "node-updates/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic", "build_flavor": (lib or _native.lib()).prl_build_flavor().decode(),
         "config": {"avg_dtype": "f32 (opt-in: PRL_SOLVER_AVG_F32; the reference's average is float64)" if args.avg_f32 else "f64",
                    "workload": "CFR+ (delay 0) on %s (%d-chip stacks%s), %d flops per GPU x %d turns x %d rivers of seeded run-outs, 1326-hand ranges"
-                               % (args.game, stack, ", pot-sized raises" if nl else "", args.flops, args.turns, args.rivers),
+                               % (args.game, stack, (", pot-sized raises" if args.bets == "POT_ONLY" else ", bet_sets.%s raises" % args.bets) if nl else "", args.flops, args.turns, args.rivers),
                    "engine": s.engine + (" (per-street)" if s.engine == "fused" else ""), "nodes": tree.n_nodes, "nodes_whole_job": n_nodes_job,
                    "placement_probe_ms_per_iteration": placement, "flops_per_gpu": args.flops, "exchanges": int(s.get("exchanges")[0]) if (world > 1 or force) else 0, "action_columns": tree.n_cols,
                    "action_columns_last_street": cols_last, "board_rows": int(tree.n_boards), "tree_build_s": t_tree,

@@ -53,6 +53,8 @@ constexpr int prl_fhp_out_width(int mode) {
 
 #define PRL_FHP_MAX_NODES 40
 #define PRL_FHP_MAX_DEC 12
+#define PRL_FHP_BOARD_MAX_ACTIONS 3  // the single-deal board pass (prl_fhp_pass.inc, its bookkeeping kernels, prl_solver's blocked-hand averages): its shapes stay at three
+#define PRL_FHP_MAX_ACTIONS 4  // actions of a decision node of any registered shape (PrlFhpDerive::MAX_A): sizes the per-node arrays of the run-time readers of dec_nch
 
 // the three arrays of a shape
 struct PrlFhpSpec15 {
@@ -90,6 +92,30 @@ struct PrlFhpSpec33 {
     static constexpr int A(int n) { constexpr int t[N_NODES] = {1, 0, -1, 1, -1, -1, 0, -1, -1, 1, -1, -1, 0, -1, -1, 1, -1, -1, 0, -1, -1, 1, -1, -1, 0, -1, -1, 1, -1, -1, 0, -1, -1}; return t[n]; }
     static constexpr int C(int n) { constexpr int t[N_NODES] = {2, 2, 0, 3, 0, 0, 3, 0, 0, 3, 0, 0, 3, 0, 0, 2, 0, 0, 3, 0, 0, 3, 0, 0, 3, 0, 0, 3, 0, 0, 2, 0, 0}; return t[n]; }
 };
+// Two raise sizes (bet_sets.B_2: pot, all-in) in DiscretizedNLHoldem, blinds 50 / 100, one post-flop street each. What is left of the stack when the street
+// starts decides the shape: a raise that would be all-in anyway merges with the all-in action, so a node has 2, 3 or 4 children. Listings from the library's
+// own tree builder (scripts/list_street_shapes.py, the walk of prl_st.cpp::list_instance); the 9-node shape of these trees is PrlFhpSpec9.
+//   15B2  stack 300:           0 seat1 {check -> 1, pot -> 9, all-in -> 12};  1 seat0 {check -> 2 leaf, pot -> 3, all-in -> 6};  3, 6, 9, 12 {fold, call}
+//   21B2  stack 600 and more:  three actions at the root and after a check, one re-raise over the pot bet
+//   33B2  stack 1200 .. 2500:  a seat that faces the first pot bet has FOUR actions (fold, call, pot, all-in): nodes 3 and 18
+struct PrlFhpSpec15B2 {
+    static constexpr int N_NODES = 15;
+    static constexpr int K(int n) { constexpr int t[N_NODES] = {0, 0, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3}; return t[n]; }
+    static constexpr int A(int n) { constexpr int t[N_NODES] = {1, 0, -1, 1, -1, -1, 1, -1, -1, 0, -1, -1, 0, -1, -1}; return t[n]; }
+    static constexpr int C(int n) { constexpr int t[N_NODES] = {3, 3, 0, 2, 0, 0, 2, 0, 0, 2, 0, 0, 2, 0, 0}; return t[n]; }
+};
+struct PrlFhpSpec21B2 {
+    static constexpr int N_NODES = 21;
+    static constexpr int K(int n) { constexpr int t[N_NODES] = {0, 0, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3}; return t[n]; }
+    static constexpr int A(int n) { constexpr int t[N_NODES] = {1, 0, -1, 1, -1, -1, 0, -1, -1, 1, -1, -1, 0, -1, -1, 1, -1, -1, 0, -1, -1}; return t[n]; }
+    static constexpr int C(int n) { constexpr int t[N_NODES] = {3, 3, 0, 3, 0, 0, 2, 0, 0, 2, 0, 0, 3, 0, 0, 2, 0, 0, 2, 0, 0}; return t[n]; }
+};
+struct PrlFhpSpec33B2 {
+    static constexpr int N_NODES = 33;
+    static constexpr int K(int n) { constexpr int t[N_NODES] = {0, 0, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3, 0, 2, 3}; return t[n]; }
+    static constexpr int A(int n) { constexpr int t[N_NODES] = {1, 0, -1, 1, -1, -1, 0, -1, -1, 1, -1, -1, 0, -1, -1, 1, -1, -1, 0, -1, -1, 1, -1, -1, 0, -1, -1, 1, -1, -1, 0, -1, -1}; return t[n]; }
+    static constexpr int C(int n) { constexpr int t[N_NODES] = {3, 3, 0, 4, 0, 0, 3, 0, 0, 2, 0, 0, 2, 0, 0, 2, 0, 0, 4, 0, 0, 3, 0, 0, 2, 0, 0, 2, 0, 0, 2, 0, 0}; return t[n]; }
+};
 // everything the walk needs, derived from a spec (all constexpr: evaluated by the compiler for the template recursion)
 template <class S>
 struct PrlFhpDerive {
@@ -126,6 +152,8 @@ struct PrlFhpDerive {
     }
     static constexpr int n_cols_() { int c = 0; for (int m = 0; m < N_NODES; ++m) c += kind(m) == PRL_NODE_DECISION ? nch(m) : 0; return c; }
     static constexpr int N_COLS = n_cols_();
+    static constexpr int max_a_() { int a = 0; for (int m = 0; m < N_NODES; ++m) a = kind(m) == PRL_NODE_DECISION && nch(m) > a ? nch(m) : a; return a; }
+    static constexpr int MAX_A = max_a_();  // the largest action count of a decision node: sizes every per-action array of the walks
     static constexpr int folder(int n) { return kind(n) == PRL_NODE_TERM_FOLD ? actor(parent(n)) : -1; }  // the seat that folded
     // slot of a terminal among a seat's terminal vectors: showdown nodes 0 .. N_SHOW-1, then the fold nodes
     static constexpr int term_slot(int n) {
@@ -157,6 +185,7 @@ inline PrlFhpShapeDesc prl_fhp_describe() {
     PrlFhpShapeDesc d = {};
     d.n_nodes = D::N_NODES; d.n_cols = D::N_COLS; d.n_dec = D::N_DEC;
     static_assert(D::N_NODES <= PRL_FHP_MAX_NODES && D::N_DEC <= PRL_FHP_MAX_DEC, "enlarge PRL_FHP_MAX_*");
+    static_assert(D::MAX_A <= PRL_FHP_MAX_ACTIONS, "a decision node with more actions than the readers of dec_nch hold (PRL_FHP_MAX_ACTIONS)");
     for (int n = 0; n < D::N_NODES; ++n) {
         d.kind[n] = D::kind(n); d.actor[n] = D::actor(n); d.nch[n] = D::nch(n); d.parent[n] = D::parent(n); d.col0[n] = D::col0(n);
         d.folder[n] = D::folder(n);

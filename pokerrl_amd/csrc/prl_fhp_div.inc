@@ -59,8 +59,10 @@ PRL_DEV PRL_INLINE void fhp_box_add(FhpBox& b, float t) {
 }
 PRL_DEV PRL_INLINE bool fhp_box_ok(const FhpBox& b) { return b.umax <= 0x48800000u /* 2^18 */ && b.umin >= 0x2B800000u - 1u /* 2^-40 */; }
 
-template <int A>
-PRL_DEV PRL_INLINE bool fhp_node_in_box(const float (&t)[3][FHP_SLOTS], const float (&sum)[FHP_SLOTS]) {
+// MA (deduced): the action bound of the caller's shape, the first extent of its per-action arrays (PrlFhpDerive::MAX_A; 3 in the board pass)
+template <int A, int MA>
+PRL_DEV PRL_INLINE bool fhp_node_in_box(const float (&t)[MA][FHP_SLOTS], const float (&sum)[FHP_SLOTS]) {
+    static_assert(A <= 3 && A <= MA, "the per-node box bounds min t / sum for a sum of at most three addends: nodes with more actions take fhp_regret_match_generic");
     unsigned ok = 1u;
     for (int k = 0; k < FHP_SLOTS; ++k) {
         const float b = sum[k] > 0.f ? sum[k] : 1.f;
@@ -71,15 +73,17 @@ PRL_DEV PRL_INLINE bool fhp_node_in_box(const float (&t)[3][FHP_SLOTS], const fl
     return ok != 0u;
 }
 
-template <int A>
-PRL_DEV PRL_INLINE void fhp_regret_match_generic(const float (&t)[3][FHP_SLOTS], const float (&sum)[FHP_SLOTS], float (&q)[3][FHP_SLOTS]) {
+template <int A, int MA>
+PRL_DEV PRL_INLINE void fhp_regret_match_generic(const float (&t)[MA][FHP_SLOTS], const float (&sum)[FHP_SLOTS], float (&q)[MA][FHP_SLOTS]) {
+    static_assert(A <= MA, "more actions than the shape's bound");
     const float unif = (float)(1.0 / (double)A);
     for (int i = 0; i < A; ++i)
         for (int k = 0; k < FHP_SLOTS; ++k) q[i][k] = sum[k] > 0.f ? t[i][k] / sum[k] : unif;
 }
 
-template <int A>
-PRL_DEV PRL_INLINE void fhp_regret_match_fast(const float (&t)[3][FHP_SLOTS], const float (&sum)[FHP_SLOTS], float (&q)[3][FHP_SLOTS]) {
+template <int A, int MA>
+PRL_DEV PRL_INLINE void fhp_regret_match_fast(const float (&t)[MA][FHP_SLOTS], const float (&sum)[FHP_SLOTS], float (&q)[MA][FHP_SLOTS]) {
+    static_assert(A <= 3 && A <= MA, "the boxes above are derived for at most three addends");
     const float unif = (float)(1.0 / (double)A);
     FhpF b, y;
     bool pos[FHP_SLOTS];
@@ -103,8 +107,9 @@ PRL_DEV PRL_INLINE void fhp_regret_match_fast(const float (&t)[3][FHP_SLOTS], co
 }
 
 // fast: WAVE-UNIFORM, true only if every lane of the wave is inside one of the boxes for this node
-template <int A>
-PRL_DEV PRL_INLINE void fhp_regret_match(const float (&t)[3][FHP_SLOTS], const float (&sum)[FHP_SLOTS], float (&q)[3][FHP_SLOTS], bool fast) {
-    if (fast) fhp_regret_match_fast<A>(t, sum, q);
-    else fhp_regret_match_generic<A>(t, sum, q);
+// (a node with four actions always divides generically: the street pass, the only walk that has such nodes, calls fhp_regret_match_generic itself)
+template <int A, int MA>
+PRL_DEV PRL_INLINE void fhp_regret_match(const float (&t)[MA][FHP_SLOTS], const float (&sum)[FHP_SLOTS], float (&q)[MA][FHP_SLOTS], bool fast) {
+    if constexpr (A <= 3) { if (fast) { fhp_regret_match_fast<A>(t, sum, q); return; } }
+    fhp_regret_match_generic<A>(t, sum, q);
 }

@@ -62,6 +62,9 @@ namespace fhp_shape21 {
 #undef FHP_LAUNCH_BOUNDS
 
 const PrlFhpShapeDesc& prl_fhp_shape_desc(int shape_id) {
+    static_assert(PrlFhpDerive<PrlFhpSpec15>::MAX_A <= PRL_FHP_BOARD_MAX_ACTIONS && PrlFhpDerive<PrlFhpSpec9>::MAX_A <= PRL_FHP_BOARD_MAX_ACTIONS &&
+                      PrlFhpDerive<PrlFhpSpec21>::MAX_A <= PRL_FHP_BOARD_MAX_ACTIONS,
+                  "the board pass and the readers of PrlFhpParams::dec_nch hold PRL_FHP_BOARD_MAX_ACTIONS actions per node");
     static const PrlFhpShapeDesc d[PRL_FHP_N_SHAPES] = {prl_fhp_describe<PrlFhpDerive<PrlFhpSpec15>>(), prl_fhp_describe<PrlFhpDerive<PrlFhpSpec9>>(),
                                                         prl_fhp_describe<PrlFhpDerive<PrlFhpSpec21>>()};
     return d[shape_id];
@@ -111,7 +114,7 @@ PRL_GLOBAL void prl_k_fhp_strategy_from_regret(PrlFhpParams prm, double* out_reg
         const size_t q = t % prm.np;
         const int A = prm.dec_nch[j], col0 = prm.dec_col0[j];
         const size_t base = (b * prm.n_cols_board + col0) * (size_t)prm.np + q;
-        float tt[3];
+        float tt[PRL_FHP_BOARD_MAX_ACTIONS];
         float sum = 0.f;
         for (int i = 0; i < A; ++i) {
             float r = prm.regret[base + (size_t)i * prm.np];
@@ -135,7 +138,7 @@ PRL_GLOBAL void prl_k_fhp_avg_from_sum(PrlFhpParams prm) {
         const size_t q = t % prm.np;
         const int A = prm.dec_nch[j], col0 = prm.dec_col0[j];
         const size_t base = (b * prm.n_cols_board + col0) * (size_t)prm.np + q;
-        float as[3];
+        float as[PRL_FHP_BOARD_MAX_ACTIONS];
         for (int i = 0; i < A; ++i) as[i] = prm.avg_sum[base + (size_t)i * prm.np];
         float sum = as[0];
         for (int i = 1; i < A; ++i) sum = sum + as[i];

@@ -131,7 +131,7 @@ struct prl_solver {
     bool sorted = false;
     int col_base = 0, ncb = 0;         // global column id of board 0's first column, columns per board
     size_t board_ofs = 0, col_elems = 0;
-    double blk_avg[4] = {0., 0., 0., 0.};  // CFR+ running average of a hand its board blocks, by action count: the board pass keeps no
+    double blk_avg[PRL_FHP_BOARD_MAX_ACTIONS + 1] = {};  // CFR+ running average of a hand its board blocks, by action count: the board pass keeps no
                                        // storage for it (regrets 0 for ever -> uniform strategy -> a scalar recurrence per action count)
     float* d_user_blocked32 = nullptr; // what set_strategy's caller had for the blocked hands, [n_boards * ncb][PRL_FHP_NBLOCKED]: get returns it
     double* d_user_blocked64 = nullptr;
@@ -376,14 +376,14 @@ static int sorted_set_boards(prl_solver* s, const void* host_cols, int elem, voi
 static void blocked_avg_fill(const prl_solver* s, double* fill) {
     for (int j = 0; j < s->ncb; ++j) {
         const int A = board_col_actions(s, j);
-        if (s->variant == PRL_CFR_PLUS) fill[j] = s->blk_avg[A < 4 ? A : 0];
+        if (s->variant == PRL_CFR_PLUS) fill[j] = s->blk_avg[A <= PRL_FHP_BOARD_MAX_ACTIONS ? A : 0];
         else fill[j] = s->board_avg_f64 ? 1.0 / (double)A : 0.0;  // prl_k_fhp_avg_from_sum on an all-zero sum, once the first sums exist
     }
 }
 // CFRPlus.py:65-87 for a hand whose regrets are 0 for ever (its strategy is the uniform float32 one): what the board pass would have stored
 static void blocked_avg_step(prl_solver* s, int mode, double m_old, double m_new) {
     if (!mode) return;
-    for (int A = 1; A < 4; ++A) {
+    for (int A = 1; A <= PRL_FHP_BOARD_MAX_ACTIONS; ++A) {
         const float unif = (float)(1.0 / (double)A);
         double a = mode == 2 ? m_old * s->blk_avg[A] + m_new * (double)unif : (double)unif;
         if (s->avg_f32) a = (double)(float)a;

@@ -71,7 +71,11 @@ float chance_weight(const PrlFlatTree& t, int chance_node, long long n_children_
 int prl_st_build(const PrlFlatTree& t, long long top_weight_children, PrlStPlanHost* out, std::string* why) {
     PrlStPlanHost& P = *out;
     P = PrlStPlanHost();
-    auto fail = [&](const char* m) { if (why) *why = m; return PRL_ERR_UNSUPPORTED; };
+    auto fail = [&](const std::string& m) { if (why) *why = m; return PRL_ERR_UNSUPPORTED; };
+    // what bounds the registered street shapes: said with every refusal of a street subtree (engine="fused" raises it, engine="auto" takes LEVELS)
+    const std::string limit = ": the per-street engine walks street shapes of at most " + std::to_string(PRL_FHP_MAX_ACTIONS) + " actions per decision (four: two raise sizes) whose "
+                              "terminal vectors fit the 160 KB LDS of a CU on the last street (bet_sets.B_2 up to 25 big blinds; deeper stacks, B_3 and wider bet sets run on the "
+                              "level-synchronous engine)";
     if (t.rules.n_hole_cards != 2 || t.rules.n_cards != 52 || t.board_len != 5) return fail("2-hole-card games on the 52-card deck with 5-card run-outs only");
     // ---- trunk: the nodes above every chance node -------------------------------------------------------------------------------
     P.trunk_col_of_node.assign(t.n_nodes, -1);
@@ -151,10 +155,15 @@ int prl_st_build(const PrlFlatTree& t, long long top_weight_children, PrlStPlanH
                     }
                     Listing ls;
                     bool hc = false, hs = false;
-                    if (!list_instance(t, root, &ls, &hc, &hs)) return fail("a street subtree larger than PRL_FHP_MAX_NODES");
+                    if (!list_instance(t, root, &ls, &hc, &hs)) return fail("a street subtree of more than PRL_FHP_MAX_NODES (" + std::to_string(PRL_FHP_MAX_NODES) + ") nodes" + limit);
                     any_chance |= hc; any_show |= hs; any_inst = true;
                     const int spec = match_spec(t, ls);
-                    if (spec < 0) return fail("a street subtree that is not one of the registered shapes (prl_st.h)");
+                    if (spec < 0) {
+                        int max_a = 0;
+                        for (int a : ls.nch) max_a = a > max_a ? a : max_a;
+                        return fail("a street subtree (" + std::to_string(ls.node.size()) + " nodes, up to " + std::to_string(max_a) +
+                                    " actions per decision) that is not one of the registered shapes (prl_st.h)" + limit);
+                    }
                     if (group_of_spec[spec] < 0) {
                         if (P.n_groups >= PRL_ST_MAX_GROUPS) return fail("more (street, shape) groups than PRL_ST_MAX_GROUPS");
                         group_of_spec[spec] = P.n_groups++;

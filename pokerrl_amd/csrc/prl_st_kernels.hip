@@ -12,7 +12,8 @@
 const PrlFhpShapeDesc& prl_st_spec_desc(int spec) {
     static const PrlFhpShapeDesc d[PRL_ST_N_SPECS] = {prl_fhp_describe<PrlFhpDerive<PrlFhpSpec9>>(), prl_fhp_describe<PrlFhpDerive<PrlFhpSpec15>>(),
                                                       prl_fhp_describe<PrlFhpDerive<PrlFhpSpec21>>(), prl_fhp_describe<PrlFhpDerive<PrlFhpSpec27>>(),
-                                                      prl_fhp_describe<PrlFhpDerive<PrlFhpSpec33>>()};
+                                                      prl_fhp_describe<PrlFhpDerive<PrlFhpSpec33>>(), prl_fhp_describe<PrlFhpDerive<PrlFhpSpec15B2>>(),
+                                                      prl_fhp_describe<PrlFhpDerive<PrlFhpSpec21B2>>(), prl_fhp_describe<PrlFhpDerive<PrlFhpSpec33B2>>()};
     return d[spec];
 }
 
@@ -23,6 +24,9 @@ int prl_launch_st_down(int spec, const PrlStParams& prm, int src0, int src1, voi
         case PRL_ST_SPEC_21: return st_spec21::launch_down(prm, src0, src1, stream);
         case PRL_ST_SPEC_27: return st_spec27::launch_down(prm, src0, src1, stream);
         case PRL_ST_SPEC_33: return st_spec33::launch_down(prm, src0, src1, stream);
+        case PRL_ST_SPEC_15_B2: return st_spec15b2::launch_down(prm, src0, src1, stream);
+        case PRL_ST_SPEC_21_B2: return st_spec21b2::launch_down(prm, src0, src1, stream);
+        case PRL_ST_SPEC_33_B2: return st_spec33b2::launch_down(prm, src0, src1, stream);
         default: return PRL_ERR_UNSUPPORTED;
     }
 }
@@ -34,6 +38,9 @@ int prl_launch_st_pass(int spec, bool last, const PrlStParams& prm, int mode, in
         case PRL_ST_SPEC_21: return st_spec21::launch_pass(last, prm, mode, src0, src1, stream);
         case PRL_ST_SPEC_27: return st_spec27::launch_pass(last, prm, mode, src0, src1, stream);
         case PRL_ST_SPEC_33: return st_spec33::launch_pass(last, prm, mode, src0, src1, stream);
+        case PRL_ST_SPEC_15_B2: return st_spec15b2::launch_pass(last, prm, mode, src0, src1, stream);
+        case PRL_ST_SPEC_21_B2: return st_spec21b2::launch_pass(last, prm, mode, src0, src1, stream);
+        case PRL_ST_SPEC_33_B2: return st_spec33b2::launch_pass(last, prm, mode, src0, src1, stream);
         default: return PRL_ERR_UNSUPPORTED;
     }
 }
@@ -93,7 +100,7 @@ PRL_GLOBAL void prl_k_st_strategy_from_regret(PrlStParams prm, PrlStDecTable dt,
         const size_t h = t % prm.R;
         const int A = dt.nch[j];
         const size_t base = ((size_t)prm.col_base + i * dt.n_cols + dt.col0[j]) * (size_t)prm.R + h;
-        float tt[3];
+        float tt[PRL_FHP_MAX_ACTIONS];  // (A <= PRL_FHP_MAX_ACTIONS: prl_fhp_describe)
         float sum = 0.f;
         for (int a = 0; a < A; ++a) {
             const float r = prm.regret[base + (size_t)a * prm.R];
@@ -112,7 +119,7 @@ PRL_GLOBAL void prl_k_st_avg_from_sum(PrlStParams prm, PrlStDecTable dt) {  // V
         const size_t h = t % prm.R;
         const int A = dt.nch[j];
         const size_t base = ((size_t)prm.col_base + i * dt.n_cols + dt.col0[j]) * (size_t)prm.R + h;
-        float as[3];
+        float as[PRL_FHP_MAX_ACTIONS];
         for (int a = 0; a < A; ++a) as[a] = prm.avg_sum[base + (size_t)a * prm.R];
         float sum = as[0];
         for (int a = 1; a < A; ++a) sum = sum + as[a];

@@ -21,6 +21,7 @@ static_assert(StShape::subtree_size(0) == StShape::N_NODES, "the spec is one DFS
 #define ST_NL (StShape::N_SHOW)   // "go on" leaves (showdowns on the last street)
 #define ST_NF (StShape::N_FOLD)
 #define ST_NCOLS (StShape::N_COLS)
+#define ST_MAXA (StShape::MAX_A)  // actions of a decision node: the first extent of every per-action array below
 static_assert(ST_NF >= 1 && ST_NL >= 1, "a street subtree has fold terminals and leaves");
 
 #include "prl_fhp_div.inc"
@@ -41,6 +42,8 @@ static_assert(sizeof(PrlStInst) == 192 && ST_INST_WORDS <= 64, "an instance reco
 template <bool LAST> constexpr size_t st_lds_bytes() {
     return ((size_t)st_nvec<LAST>() * st_npad<LAST>() + (LAST ? (size_t)ST_NL * st_npad<LAST>() : 0) + (size_t)ST_NF * 64 + 32 + 2 * ST_INST_WORDS) * 4;
 }
+// any registered shape may turn up on the last street, where the showdown vectors and their corrections join the fold vectors in LDS
+static_assert(st_lds_bytes<true>() <= 160 * 1024 && st_lds_bytes<false>() <= 160 * 1024, "this shape does not fit the CU's LDS on the last street: it cannot be registered");
 
 // ---- global access helpers: a lane owns the two adjacent hands 2 tid, 2 tid + 1 (one 8 / 16-byte access) ------------------------
 // address of a lane's pair in an array whose row pointer is wave-uniform: a uniform 64-bit base plus a 32-bit unsigned BYTE offset per lane, the
@@ -196,9 +199,9 @@ PRL_DEV PRL_INLINE void st_load_avg_sum_from(const C& c, StAvgPre& AP) {
 }
 
 template <int SRC, int A, class S, class C>
-PRL_DEV PRL_INLINE void st_node_strategy(const C& c, const StRegs& R, int col0, S (&s)[3][2]) {
+PRL_DEV PRL_INLINE void st_node_strategy(const C& c, const StRegs& R, int col0, S (&s)[ST_MAXA][2]) {
     if constexpr (SRC == PRL_SRC_REGRET) {
-        float t[3][2], sum[2], q[3][2];
+        float t[ST_MAXA][2], sum[2], q[ST_MAXA][2];
         for (int k = 0; k < 2; ++k) {
             for (int i = 0; i < A; ++i) {
                 const float r = R.rg[col0 + i][k];
@@ -236,17 +239,15 @@ struct StPush {
         } else if constexpr (kind == PRL_NODE_DECISION) {
             constexpr int a = StShape::actor(NODE), A = StShape::nch(NODE), SRC = a == 0 ? S0 : S1, col0 = StShape::col0(NODE);
             typedef typename StScalar<SRC>::type S;
-            S s[3][2];
+            S s[ST_MAXA][2];
             st_node_strategy<SRC, A, S>(c, R, col0, s);
-#define ST_PUSH_KID(i)                                                                                                   \
-    if constexpr ((i) < A) {                                                                                             \
-        StV cr;                                                                                                          \
-        for (int k = 0; k < 2; ++k) cr.v[k] = st_mul_reach(s[i][k], a == 0 ? r0.v[k] : r1.v[k]);                         \
-        if constexpr (a == 0) StPush<S0, S1, StShape::child(NODE, (i))>::run(c, R, out, cr, r1);                         \
-        else StPush<S0, S1, StShape::child(NODE, (i))>::run(c, R, out, r0, cr);                                          \
-    }
-            ST_PUSH_KID(0) ST_PUSH_KID(1) ST_PUSH_KID(2)
-#undef ST_PUSH_KID
+            st_static_for<0, A>([&](auto ic) {
+                constexpr int I = decltype(ic)::value, KID = StShape::child(NODE, I);
+                StV cr;
+                for (int k = 0; k < 2; ++k) cr.v[k] = st_mul_reach(s[I][k], a == 0 ? r0.v[k] : r1.v[k]);
+                if constexpr (a == 0) StPush<S0, S1, KID>::run(c, R, out, cr, r1);
+                else StPush<S0, S1, KID>::run(c, R, out, r0, cr);
+            });
         }
     }
 };
@@ -309,7 +310,7 @@ struct StDown {
             if constexpr (a == Q) {
                 constexpr int SRC = Q == 0 ? S0 : S1, col0 = StShape::col0(NODE);
                 typedef typename StScalar<SRC>::type S;
-                S s[3][2];
+                S s[ST_MAXA][2];
                 st_node_strategy<SRC, A, S>(c, R, col0, s);
                 if (c.avgsum_mask() & (1 << Q)) {  // VanillaCFR.py:40-55, LinearCFR.py:41-57: avg_sum += strategy * reach [* (t + 1)]
                     const int it = c.prm->avgsum_iter[Q];
@@ -323,18 +324,14 @@ struct StDown {
                         st_gstore(st_at(c.prm->avg_sum + (c.col_base_i + col0 + i) * (size_t)c.prm->R, c.gofs), as);
                     }
                 }
-#define ST_DOWN_KID(i)                                                                                                   \
-    if constexpr ((i) < A) {                                                                                             \
-        StV cr;                                                                                                          \
-        for (int k = 0; k < 2; ++k) cr.v[k] = st_mul_reach(s[i][k], rq.v[k]);                                            \
-        StDown<LAST, Q, S0, S1, StShape::child(NODE, (i))>::run(c, R, AP, cr);                                           \
-    }
-                ST_DOWN_KID(0) ST_DOWN_KID(1) ST_DOWN_KID(2)
-#undef ST_DOWN_KID
+                st_static_for<0, A>([&](auto ic) {
+                    constexpr int I = decltype(ic)::value;
+                    StV cr;
+                    for (int k = 0; k < 2; ++k) cr.v[k] = st_mul_reach(s[I][k], rq.v[k]);
+                    StDown<LAST, Q, S0, S1, StShape::child(NODE, I)>::run(c, R, AP, cr);
+                });
             } else {
-                if constexpr (A > 0) StDown<LAST, Q, S0, S1, StShape::child(NODE, 0)>::run(c, R, AP, rq);
-                if constexpr (A > 1) StDown<LAST, Q, S0, S1, StShape::child(NODE, 1)>::run(c, R, AP, rq);
-                if constexpr (A > 2) StDown<LAST, Q, S0, S1, StShape::child(NODE, 2)>::run(c, R, AP, rq);
+                st_static_for<0, A>([&](auto ic) { StDown<LAST, Q, S0, S1, StShape::child(NODE, decltype(ic)::value)>::run(c, R, AP, rq); });
             }
         }
     }
@@ -651,17 +648,18 @@ struct StUp {
         } else {
             constexpr int a = StShape::actor(NODE), A = StShape::nch(NODE), col0 = StShape::col0(NODE);
             constexpr bool UPD = a == P && prl_fhp_updates(MODE, P);
-            StV ce[3], cb[3];
-            if constexpr (A > 0) StUp<LAST, ROWMODE, MODE, P, S0, S1, StShape::child(NODE, 0), TC>::run(c, R, ce[0], cb[0]);
-            if constexpr (A > 1) StUp<LAST, ROWMODE, MODE, P, S0, S1, StShape::child(NODE, 1), TC>::run(c, R, ce[1], cb[1]);
-            if constexpr (A > 2) StUp<LAST, ROWMODE, MODE, P, S0, S1, StShape::child(NODE, 2), TC>::run(c, R, ce[2], cb[2]);
+            StV ce[ST_MAXA], cb[ST_MAXA];
+            st_static_for<0, A>([&](auto ic) {
+                constexpr int I = decltype(ic)::value;
+                StUp<LAST, ROWMODE, MODE, P, S0, S1, StShape::child(NODE, I), TC>::run(c, R, ce[I], cb[I]);
+            });
             if constexpr (a == P) {
                 constexpr int SRC = P == 0 ? S0 : S1;
                 typedef typename StScalar<SRC>::type S;
-                S s[3][2];
+                S s[ST_MAXA][2];
                 st_node_strategy<SRC, A, S>(c, R, col0, s);
                 if constexpr (sizeof(S) == sizeof(float)) {
-                    FhpF sv[3];
+                    FhpF sv[ST_MAXA];
                     for (int i = 0; i < A; ++i)
                         for (int k = 0; k < 2; ++k) sv[i][k] = (float)s[i][k];
                     FhpF acc = sv[0] * ce[0].v;
@@ -680,7 +678,7 @@ struct StUp {
                     br.v[k] = mx;
                 }
                 if constexpr (UPD) {  // _CFRBase.py:146-185 + CFRPlus.py:37-41 / VanillaCFR.py:26-30 / LinearCFR.py:27-31
-                    float rn[3][2];
+                    float rn[ST_MAXA][2];
                     for (int i = 0; i < A; ++i) {
                         const FhpF d = ce[i].v - ev.v;
                         FhpF rv = d;
@@ -698,7 +696,7 @@ struct StUp {
                     }
                     constexpr bool KEEP = MODE == PRL_FHP_UPDATE1_EVAL1;
                     if (KEEP || c.avg_mode()) {
-                        float t[3][2], sum[2];
+                        float t[ST_MAXA][2], sum[2];
                         for (int k = 0; k < 2; ++k) {
                             sum[k] = 0.f;
                             for (int i = 0; i < A; ++i) {
@@ -706,7 +704,7 @@ struct StUp {
                                 sum[k] = sum[k] + t[i][k];
                             }
                         }
-                        float qn[3][2];
+                        float qn[ST_MAXA][2];
                         fhp_regret_match_generic<A>(t, sum, qn);
                         for (int i = 0; i < A; ++i) {
                             double an[2];
@@ -1019,4 +1017,5 @@ int launch_pass(bool last, const PrlStParams& prm, int mode, int src0, int src1,
 #undef ST_NL
 #undef ST_NF
 #undef ST_NCOLS
+#undef ST_MAXA
 #undef ST_NLIVE_LAST

@@ -23,3 +23,6 @@ PRL_ST_DECLARE_SPEC(st_spec15)
 PRL_ST_DECLARE_SPEC(st_spec21)
 PRL_ST_DECLARE_SPEC(st_spec27)
 PRL_ST_DECLARE_SPEC(st_spec33)
+PRL_ST_DECLARE_SPEC(st_spec15b2)
+PRL_ST_DECLARE_SPEC(st_spec21b2)
+PRL_ST_DECLARE_SPEC(st_spec33b2)
