@@ -475,6 +475,8 @@ enum {
                                                          elsewhere) and the bytes they hold; {0, 0}: plain hipMalloc */
     PRL_SF_AVG_PAIRS = 19,   /* int64                    pairs of iterations whose CFR+ board-average updates shared one pass over the float64
                                                          columns so far (prl_solver_iterations; 0 wherever pairing does not apply)          */
+    PRL_SF_AVG_SPLIT_PAIRS = 20, /* int64                such pairs of the decision nodes of set B completed one iteration behind set A's (split pairs:
+                                                         PRL_SF_AVG_PAIRS then counts set A's; 0 while the whole board pairs in one phase)   */
     PRL_SF_EXPLICIT_STRATEGY = 16 /* int32               fused engines: -1 strategy follows regrets / uniform fill, 0 an explicit float32
                                                          strategy is loaded (prl_solver_set_strategy), 1 an explicit float64 one; LEVELS: -1 */
 };

@@ -227,7 +227,9 @@ struct PrlFhpParams {
     double m_old, m_new;        // CFRPlus.py:65-87 weights (float64)
     // paired CFR+ average updates (prl_solver_iterations; prl_fhp_pass.inc, FhpCtxT): PRL_FHP_AVG_DEFERRED -- this iteration's update passes leave the
     // board average alone; PRL_FHP_AVG_CATCH_UP -- they first apply the previous iteration's step with its weights below, then their own
-    int32_t avg_pair;
+    // avg_pair_b: the same switch for the decision nodes of set B (prl_fhp_pass.inc: fhp_avg_set), avg_pair then speaks for set A alone -- split pairs,
+    // B's pair phase one iteration behind A's. Equal values: the whole board in one phase
+    int32_t avg_pair, avg_pair_b;
     double m_old_prev, m_new_prev;
     // Vanilla / Linear CFR: the reach-weighted average of seat q needs q's NEW reach, known only after the trunk update that
     // follows q's pass -- so it rides on the next pass that walks q's reach (phase B for seat q): bit q of avgsum_mask
@@ -249,6 +251,8 @@ struct PrlFhpParams {
 int prl_fhp_match_shape(const PrlFlatTree& t, int* chance_node, int* first_board_node, int* col_base, float* pots /*[PRL_FHP_MAX_NODES]*/);
 
 int prl_launch_fhp_pass(const PrlFhpParams& prm, int mode, int src0, int src1, void* stream);
+// does the shape's board pass have the pair kinds of split CFR+ average pairs (prl_fhp_kernels.hip: FHP_AVG_SPLIT)?
+bool prl_fhp_avg_split_supported(int shape_id);
 // the strategy the regrets imply, board region -> board region (float64)
 void prl_launch_fhp_strategy_from_regret(const PrlFhpParams& prm, double* out_region, void* stream);
 void prl_launch_fhp_avg_from_sum(const PrlFhpParams& prm, void* stream);

@@ -40,6 +40,10 @@
 #define FHP_THREADS 768
 #define FHP_SLOTS 2
 #define FHP_LAUNCH_BOUNDS FHP_LB(768, 3)
+// FHP_AVG_SPLIT: the shape has the pair kinds of split CFR+ average pairs (prl_fhp_pass.inc: fhp_steady_pair). FHP15 and FHP9 do, without vector
+// spills. FHP21 does not: its UPDATE0_BR under (catch-up, deferred) spills 21 VGPRs where the whole-board kinds spill 19, so its boards keep pairing
+// in one phase (prl_fhp_avg_split_supported: prl_solver_iterations asks before it shifts set B)
+#define FHP_AVG_SPLIT 1
 #define FHP_SPEC PrlFhpSpec15
 namespace fhp_shape15 {
 #include "prl_fhp_pass.inc"
@@ -51,6 +55,8 @@ namespace fhp_shape9 {
 }
 #undef FHP_SPEC
 #if !defined(PRL_FHP_NO_SHAPE21)
+#undef FHP_AVG_SPLIT
+#define FHP_AVG_SPLIT 0
 #define FHP_SPEC PrlFhpSpec21
 namespace fhp_shape21 {
 #include "prl_fhp_pass.inc"
@@ -60,6 +66,9 @@ namespace fhp_shape21 {
 #undef FHP_THREADS
 #undef FHP_SLOTS
 #undef FHP_LAUNCH_BOUNDS
+#undef FHP_AVG_SPLIT
+
+bool prl_fhp_avg_split_supported(int shape_id) { return shape_id == PRL_FHP_SHAPE_15 || shape_id == PRL_FHP_SHAPE_9; }
 
 const PrlFhpShapeDesc& prl_fhp_shape_desc(int shape_id) {
     static_assert(PrlFhpDerive<PrlFhpSpec15>::MAX_A <= PRL_FHP_BOARD_MAX_ACTIONS && PrlFhpDerive<PrlFhpSpec9>::MAX_A <= PRL_FHP_BOARD_MAX_ACTIONS &&

@@ -248,9 +248,43 @@ PRL_DEV PRL_INLINE FhpLds fhp_lds() {
 // divisions where nothing else needs them, no average stores) and t + 1 applies both steps in registers (CATCH-UP: the node's old strategy s[i][k],
 // already there for the EV, with iteration t's weights, then its own step): the same operations in the same order with the same roundings, one HBM
 // round trip of the float64 columns instead of two. STEADY 5 / 6 are the two as compile-time kinds; the generic instantiation asks at run time.
-constexpr bool fhp_steady_plus(int steady) { return steady == 1 || steady == 4 || steady == 5 || steady == 6; }
-template <int STEADY>  // 0 generic; 1 CFR+, 2 Linear CFR, 3 vanilla CFR in their steady state; 4 CFR+ with the float32 average; 5 / 6 CFR+ deferred / catch-up
+//
+// SPLIT PAIRS (PrlFhpParams::avg_pair_b). The recurrence is per column, so nothing forces all of a seat's columns into the same pair phase: a seat's
+// decision nodes are split at compile time into set A and set B (fhp_avg_set: balanced column counts), B's pairs run one iteration behind A's, and every
+// launch of a long call carries the float64 round trip of about half a seat's columns instead of all (catch-up) or none (deferred) of them. The steady
+// kind is then a PAIR (kind of A, kind of B) of 1 (unpaired) / 5 (deferred) / 6 (catch-up), STEADY = fhp_steady_pair(ka, kb); equal kinds are the
+// whole-board kinds 1 / 5 / 6 themselves. Which nodes load and store an average is a compile-time property of (STEADY, node) in every steady kind.
+constexpr int FHP_STEADY_PAIR0 = 16;
+constexpr int fhp_kind_code(int k) { return k == 1 ? 0 : k == 5 ? 1 : 2; }
+constexpr int fhp_steady_pair(int ka, int kb) { return ka == kb ? ka : FHP_STEADY_PAIR0 + 4 * fhp_kind_code(ka) + fhp_kind_code(kb); }
+constexpr int fhp_code_kind(int c) { return c == 0 ? 1 : c == 1 ? 5 : 6; }
+constexpr int fhp_set_kind(int steady, int set) {  // the kind that the nodes of set 0 (A) / 1 (B) run under
+    return steady < FHP_STEADY_PAIR0 ? steady : fhp_code_kind(set == 0 ? (steady - FHP_STEADY_PAIR0) / 4 : (steady - FHP_STEADY_PAIR0) % 4);
+}
+constexpr bool fhp_steady_plus(int steady) { return steady == 1 || steady == 4 || steady == 5 || steady == 6 || steady >= FHP_STEADY_PAIR0; }
+// Set of a decision node, 0 = A, 1 = B: the seat's nodes by falling action count (DFS order among equals), each into the set that holds fewer columns
+// so far, B on a tie. FHP15: per seat 2 + 2 + 3 columns, A = the two two-action nodes, B = the three-action node; FHP9 2 | 2; FHP21 5 | 5.
+constexpr int fhp_avg_set(int n) {
+    int cols[2] = {0, 0};
+    for (int a = PrlFhpShape::MAX_A; a >= 1; --a)
+        for (int m = 0; m < PrlFhpShape::N_NODES; ++m)
+            if (PrlFhpShape::kind(m) == PRL_NODE_DECISION && PrlFhpShape::actor(m) == PrlFhpShape::actor(n) && PrlFhpShape::nch(m) == a) {
+                const int set = cols[1] <= cols[0] ? 1 : 0;
+                if (m == n) return set;
+                cols[set] += a;
+            }
+    return 0;
+}
+// does decision node n load (and store) a blended average under this kind? The generic kind may: it asks at run time.
+constexpr bool fhp_may_load_avg(int steady, int n) {
+    if (steady == 0) return true;
+    const int k = fhp_set_kind(steady, fhp_avg_set(n));
+    return k == 1 || k == 4 || k == 6;
+}
+template <int STEADY>  // 0 generic; 1 CFR+, 2 Linear CFR, 3 vanilla CFR in their steady state; 4 CFR+ with the float32 average; 5 / 6 CFR+ deferred / catch-up;
+                       // fhp_steady_pair(ka, kb): CFR+ with set A under kind ka and set B under kb
 struct FhpCtxT {
+    static constexpr int steady = STEADY;
     // Where the own float32 columns of the first batch are requested from HBM (opponent-only prefetch). At the board start wherever phase B has no
     // run-time branches around vector-memory operations (the CFR+ steady state; strategies that are not regret-matched): three phases of cover and an
     // empty memory queue. After phase B otherwise: the pending Vanilla / Linear average update of the opponent's walk sits behind a run-time test, the
@@ -264,13 +298,20 @@ struct FhpCtxT {
         else return variant_;
     }
     PRL_DEV PRL_INLINE bool first_iteration() const { if constexpr (STEADY != 0) return false; else return iter == 0; }
+    // per decision node (its set decides): how its average columns are updated by this pass
+    template <int NODE>
     PRL_DEV PRL_INLINE int avg_mode() const {
-        if constexpr (STEADY == 1 || STEADY == 4 || STEADY == 6) return 2;
-        else if constexpr (STEADY != 0) return 0;
-        else return prm->avg_pair == PRL_FHP_AVG_DEFERRED ? 0 : prm->avg_mode;
+        constexpr int set = fhp_avg_set(NODE);
+        if constexpr (STEADY == 0) return (set == 0 ? prm->avg_pair : prm->avg_pair_b) == PRL_FHP_AVG_DEFERRED ? 0 : prm->avg_mode;
+        else return fhp_may_load_avg(STEADY, NODE) ? 2 : 0;
     }
     // the blend first applies the previous iteration's step, which that iteration left out (avg_mode() == 2 whenever this holds)
-    PRL_DEV PRL_INLINE bool avg_catch_up() const { if constexpr (STEADY == 6) return true; else if constexpr (STEADY != 0) return false; else return prm->avg_pair == PRL_FHP_AVG_CATCH_UP; }
+    template <int NODE>
+    PRL_DEV PRL_INLINE bool avg_catch_up() const {
+        constexpr int set = fhp_avg_set(NODE);
+        if constexpr (STEADY == 0) return (set == 0 ? prm->avg_pair : prm->avg_pair_b) == PRL_FHP_AVG_CATCH_UP;
+        else return fhp_set_kind(STEADY, set) == 6;
+    }
     PRL_DEV PRL_INLINE int avgsum_mask() const { if constexpr (fhp_steady_plus(STEADY)) return 0; else return prm->avgsum_mask; }
     // the running average is stored as float32 (opt-in): STEADY 4 = the CFR+ steady state with it; the generic instantiation asks at run time
     PRL_DEV PRL_INLINE bool avg32() const { if constexpr (STEADY == 4) return true; else if constexpr (STEADY != 0) return false; else return prm->avg32 != nullptr; }
@@ -562,28 +603,30 @@ PRL_DEV PRL_INLINE void fhp_scan_phases(C& c, F&& between_c_and_d) {
 // them -- with ~700 cycles of cover for an HBM round trip. Pipelined order: the first two nodes of seat P in completion order are
 // requested when the walk starts, and the completion of the r-th requests the (r+2)-th: every request has at least four terminal
 // evaluations of cover, and at most two nodes' columns are in flight (the same peak as before, when the root's columns were in
-// flight for the whole walk).
+// flight for the whole walk). The ranks count the nodes that load an average under the pass's kind (fhp_may_load_avg: with split pairs a set
+// that is deferred takes no part, and the pipeline runs over the other set's nodes alone).
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr bool fhp_is_dec_of(int P, int n) { return PrlFhpShape::kind(n) == PRL_NODE_DECISION && PrlFhpShape::actor(n) == P; }
 constexpr bool fhp_completes_before(int a, int b) {  // DFS pre-order numbering: a's subtree is [a, a + size(a))
     if (a > b) return a < b + PrlFhpShape::subtree_size(b);   // a inside b's subtree
     return !(b < a + PrlFhpShape::subtree_size(a));            // a before b and b not inside a's subtree
 }
-constexpr int fhp_completion_rank(int P, int n) {
+constexpr int fhp_completion_rank(int steady, int P, int n) {
     int r = 0;
     for (int m = 0; m < PrlFhpShape::N_NODES; ++m)
-        if (m != n && fhp_is_dec_of(P, m) && fhp_completes_before(m, n)) ++r;
+        if (m != n && fhp_is_dec_of(P, m) && fhp_may_load_avg(steady, m) && fhp_completes_before(m, n)) ++r;
     return r;
 }
-constexpr int fhp_node_of_rank(int P, int r) {
+constexpr int fhp_node_of_rank(int steady, int P, int r) {
     for (int m = 0; m < PrlFhpShape::N_NODES; ++m)
-        if (fhp_is_dec_of(P, m) && fhp_completion_rank(P, m) == r) return m;
+        if (fhp_is_dec_of(P, m) && fhp_may_load_avg(steady, m) && fhp_completion_rank(steady, P, m) == r) return m;
     return -1;
 }
 template <int NODE, class C>
 PRL_DEV PRL_INLINE void fhp_request_old_average(C& c) {
     if constexpr (NODE >= 0) {
         constexpr int col0 = PrlFhpShape::col0(NODE);
+        if (c.template avg_mode<NODE>() == 2)
 #pragma unroll
         for (int i = 0; i < PrlFhpShape::nch(NODE); ++i)
         {
@@ -670,7 +713,7 @@ struct FhpUp {
             constexpr bool UPD = a == P && prl_fhp_updates(MODE, P);
             if constexpr (UPD) {
                 // old request order (kept for the run-time toggle): when the walk enters the node
-                if (c.avg_mode() == 2 && !FHP_AVG_PIPELINED(c)) fhp_request_old_average<NODE>(c);
+                if (!FHP_AVG_PIPELINED(c)) fhp_request_old_average<NODE>(c);
             }
             FhpV ce[3], cb[3];
             FhpUp<MODE, P, S0, S1, PrlFhpShape::child(NODE, 0), TC>::run(c, R, ce[0], cb[0]);
@@ -722,7 +765,8 @@ struct FhpUp {
                     // (CFRPlus.py:43-87: avg = m_old * avg + m_new * strategy, float64), and UPDATE1_EVAL1's second phase E
                     // plays it -- the register file switches from regrets to strategies for this node's columns
                     constexpr bool KEEP = MODE == PRL_FHP_UPDATE1_EVAL1;
-                    if (KEEP || c.avg_mode()) {
+                    const int avg_mode = c.template avg_mode<NODE>();
+                    if (KEEP || avg_mode) {
                         float t[3][FHP_SLOTS], sum[FHP_SLOTS];
                         for (int k = 0; k < FHP_SLOTS; ++k) {
                             sum[k] = 0.f;
@@ -745,11 +789,11 @@ struct FhpUp {
                                 if (KEEP) R.rg[col0 + i][k] = sn;
                                 double ao = c.av_old[col0 + i][k];
                                 if constexpr (SRC == PRL_SRC_REGRET) {  // (the step iteration t - 1 deferred: its strategy is the one this node just played)
-                                    if (c.avg_catch_up()) ao = c.prm->m_old_prev * ao + c.prm->m_new_prev * (double)s[i][k];
+                                    if (c.template avg_catch_up<NODE>()) ao = c.prm->m_old_prev * ao + c.prm->m_new_prev * (double)s[i][k];
                                 }
-                                an[k] = c.avg_mode() == 2 ? c.prm->m_old * ao + c.prm->m_new * (double)sn : (double)sn;
+                                an[k] = avg_mode == 2 ? c.prm->m_old * ao + c.prm->m_new * (double)sn : (double)sn;
                             }
-                            if (c.avg_mode()) {
+                            if (avg_mode) {
                                 if (c.avg32()) {
                                     float af[FHP_SLOTS];
                                     for (int k = 0; k < FHP_SLOTS; ++k) af[k] = (float)an[k];
@@ -758,7 +802,9 @@ struct FhpUp {
                             }
                         }
                     }
-                    if (c.avg_mode() == 2 && FHP_AVG_PIPELINED(c)) fhp_request_old_average<fhp_node_of_rank(P, fhp_completion_rank(P, NODE) + 2)>(c);
+                    if constexpr (fhp_may_load_avg(C::steady, NODE)) {
+                        if (FHP_AVG_PIPELINED(c)) fhp_request_old_average<fhp_node_of_rank(C::steady, P, fhp_completion_rank(C::steady, P, NODE) + 2)>(c);
+                    }
                 }
             } else {
                 FhpF acc = ce[0].v, accb = cb[0].v;
@@ -866,9 +912,9 @@ PRL_DEV PRL_INLINE void fhp_seat(C& c, FhpRegs& R, const FhpV& r_opp, FhpV& ev, 
     FHP_TICK(c, 3);
     if (c.active) {
         if constexpr (prl_fhp_updates(MODE, P)) {
-            if (c.avg_mode() == 2 && FHP_AVG_PIPELINED(c)) {
-                fhp_request_old_average<fhp_node_of_rank(P, 0)>(c);
-                fhp_request_old_average<fhp_node_of_rank(P, 1)>(c);
+            if (FHP_AVG_PIPELINED(c)) {
+                fhp_request_old_average<fhp_node_of_rank(C::steady, P, 0)>(c);
+                fhp_request_old_average<fhp_node_of_rank(C::steady, P, 1)>(c);
             }
         }
         if constexpr (MODE == PRL_FHP_UPDATE1_EVAL1) {
@@ -1141,6 +1187,13 @@ static void fhp_launch_t(const PrlFhpParams& prm, int grid, void* stream) {
     PRL_LAUNCH((prl_k_fhp_pass<MODE, S0, S1, STEADY>), grid, FHP_THREADS, FHP_LDS_BYTES, stream, prm);
 }
 
+// a pair kind of split average pairs; shapes built without them (FHP_AVG_SPLIT 0) take the generic kernel, which asks for each set's kind at run time
+template <int MODE, int STEADY>
+static void fhp_launch_split_t(const PrlFhpParams& prm, int grid, void* stream) {
+    if constexpr (FHP_AVG_SPLIT) fhp_launch_t<MODE, PRL_SRC_REGRET, PRL_SRC_REGRET, STEADY>(prm, grid, stream);
+    else fhp_launch_t<MODE, PRL_SRC_REGRET, PRL_SRC_REGRET>(prm, grid, stream);
+}
+
 int launch_pass(const PrlFhpParams& prm, int mode, int src0, int src1, void* stream) {
     if (prm.n_boards <= 0) return PRL_OK;
     if (prm.R != FHP_R) return PRL_ERR_UNSUPPORTED;  // the LDS prefetch area is laid out for 1326-hand ranges
@@ -1148,10 +1201,11 @@ int launch_pass(const PrlFhpParams& prm, int mode, int src0, int src1, void* str
     static_assert(FHP_NVEC <= 16 && FHP_LDS_BYTES <= 160 * 1024, "terminal vectors + prefetch area of this shape must fit the CU's LDS");
     int grid = prm.n_boards < prm.max_grid ? prm.n_boards : prm.max_grid;
     const int key = mode * 100 + src0 * 10 + src1;
+    auto kind_of = [](int pair) { return pair == PRL_FHP_AVG_DEFERRED ? 5 : pair == PRL_FHP_AVG_CATCH_UP ? 6 : 1; };
     // steady-state kinds (FhpCtxT): CFR+ blending its running average, or Linear / vanilla CFR, after the first iteration
     const int steady = prm.no_steady || prm.iter == 0 ? 0
                        : (prm.variant == PRL_CFR_PLUS && prm.avg_mode == 2 && prm.avgsum_mask == 0)
-                           ? (prm.avg32 ? 4 : prm.avg_pair == PRL_FHP_AVG_DEFERRED ? 5 : prm.avg_pair == PRL_FHP_AVG_CATCH_UP ? 6 : 1)
+                           ? (prm.avg32 ? 4 : fhp_steady_pair(kind_of(prm.avg_pair), kind_of(prm.avg_pair_b)))
                        : (prm.variant == PRL_CFR_LINEAR && prm.avg_mode == 0) ? 2
                        : (prm.variant == PRL_CFR_VANILLA && prm.avg_mode == 0) ? 3 : 0;
     switch (key) {
@@ -1160,12 +1214,18 @@ int launch_pass(const PrlFhpParams& prm, int mode, int src0, int src1, void* str
         case PRL_FHP_UPDATE0 * 100 + PRL_SRC_REGRET * 10 + PRL_SRC_REGRET: fhp_launch_t<PRL_FHP_UPDATE0, PRL_SRC_REGRET, PRL_SRC_REGRET>(prm, grid, stream); break;
         case PRL_FHP_UPDATE1 * 100 + PRL_SRC_REGRET * 10 + PRL_SRC_REGRET: fhp_launch_t<PRL_FHP_UPDATE1, PRL_SRC_REGRET, PRL_SRC_REGRET>(prm, grid, stream); break;
         case PRL_FHP_UPDATE0_EVAL * 100 + PRL_SRC_REGRET * 10 + PRL_SRC_REGRET: fhp_launch_t<PRL_FHP_UPDATE0_EVAL, PRL_SRC_REGRET, PRL_SRC_REGRET>(prm, grid, stream); break;
-        // the two passes of a steady-state iteration have a CFR+ specialisation (FhpCtxT)
+        // the two passes of a steady-state iteration have a CFR+ specialisation (FhpCtxT); the pairs of unequal kinds are the ones the split schedule
+        // of prl_solver_iterations takes: (D,U) opens a call, (C,D) / (D,C) alternate, (C,U) / (U,C) close it. Any other pair: the generic kernel
         case PRL_FHP_UPDATE0_BR * 100 + PRL_SRC_REGRET * 10 + PRL_SRC_REGRET:
             if (steady == 1) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 1>(prm, grid, stream);
             else if (steady == 4) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 4>(prm, grid, stream);
             else if (steady == 5) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 5>(prm, grid, stream);
             else if (steady == 6) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 6>(prm, grid, stream);
+            else if (steady == fhp_steady_pair(5, 1)) fhp_launch_split_t<PRL_FHP_UPDATE0_BR, fhp_steady_pair(5, 1)>(prm, grid, stream);
+            else if (steady == fhp_steady_pair(6, 5)) fhp_launch_split_t<PRL_FHP_UPDATE0_BR, fhp_steady_pair(6, 5)>(prm, grid, stream);
+            else if (steady == fhp_steady_pair(5, 6)) fhp_launch_split_t<PRL_FHP_UPDATE0_BR, fhp_steady_pair(5, 6)>(prm, grid, stream);
+            else if (steady == fhp_steady_pair(6, 1)) fhp_launch_split_t<PRL_FHP_UPDATE0_BR, fhp_steady_pair(6, 1)>(prm, grid, stream);
+            else if (steady == fhp_steady_pair(1, 6)) fhp_launch_split_t<PRL_FHP_UPDATE0_BR, fhp_steady_pair(1, 6)>(prm, grid, stream);
             else if (steady == 2) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 2>(prm, grid, stream);
             else if (steady == 3) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 3>(prm, grid, stream);
             else fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET>(prm, grid, stream);
@@ -1175,6 +1235,11 @@ int launch_pass(const PrlFhpParams& prm, int mode, int src0, int src1, void* str
             else if (steady == 4) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 4>(prm, grid, stream);
             else if (steady == 5) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 5>(prm, grid, stream);
             else if (steady == 6) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 6>(prm, grid, stream);
+            else if (steady == fhp_steady_pair(5, 1)) fhp_launch_split_t<PRL_FHP_UPDATE1_EVAL1, fhp_steady_pair(5, 1)>(prm, grid, stream);
+            else if (steady == fhp_steady_pair(6, 5)) fhp_launch_split_t<PRL_FHP_UPDATE1_EVAL1, fhp_steady_pair(6, 5)>(prm, grid, stream);
+            else if (steady == fhp_steady_pair(5, 6)) fhp_launch_split_t<PRL_FHP_UPDATE1_EVAL1, fhp_steady_pair(5, 6)>(prm, grid, stream);
+            else if (steady == fhp_steady_pair(6, 1)) fhp_launch_split_t<PRL_FHP_UPDATE1_EVAL1, fhp_steady_pair(6, 1)>(prm, grid, stream);
+            else if (steady == fhp_steady_pair(1, 6)) fhp_launch_split_t<PRL_FHP_UPDATE1_EVAL1, fhp_steady_pair(1, 6)>(prm, grid, stream);
             else if (steady == 2) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 2>(prm, grid, stream);
             else if (steady == 3) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 3>(prm, grid, stream);
             else fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET>(prm, grid, stream);

@@ -102,7 +102,8 @@ struct prl_solver {
     float* d_avg32 = nullptr;   // opt-in (PRL_SOLVER_AVG_F32): the board columns' running average stored as float32, [full_cols][R]
     bool avg_f32 = false;
     long long n_exchanges = 0;  // all-gathers done so far (PRL_SF_EXCHANGES)
-    long long n_avg_pairs = 0;  // paired CFR+ average updates completed so far (PRL_SF_AVG_PAIRS)
+    long long n_avg_pairs = 0;  // paired CFR+ average updates completed so far (PRL_SF_AVG_PAIRS; with split pairs: set A's)
+    long long n_avg_split_pairs = 0;  // ... and set B's pairs completed one iteration behind set A's (PRL_SF_AVG_SPLIT_PAIRS)
     void* rccl_comm = nullptr;  // sharded solve with the library's own exchange (prl_solver_create_sharded_rccl): ncclComm_t
     // ---- per-street fused engine (prl_st.h): `fused` with the board pass replaced by a sweep over the streets ----
     bool streets = false;
@@ -1904,8 +1905,9 @@ int32_t prl_solver_compute_ev(prl_solver_t* s) {  // PublicTree.compute_ev (Publ
 // trunk is updated with the summed chance-node values; a third (best-response) pass yields the exploitability.
 // avg_pair (prl_fhp.h: PRL_FHP_AVG_*, chosen by prl_solver_iterations): the board passes of this iteration leave the boards' CFR+ average alone
 // (DEFERRED), or apply the previous iteration's step before their own (CATCH_UP). Everything else -- the trunk's average, the blocked hands'
-// recurrence, the exploitability bookkeeping -- is per iteration as ever.
-static int iteration_core(prl_solver* s, bool closing_eval, int avg_pair = PRL_FHP_AVG_NORMAL) {
+// recurrence, the exploitability bookkeeping -- is per iteration as ever. avg_pair_b: the same for the decision nodes of set B when their pairs run one
+// iteration behind set A's (split pairs; -1 = as set A: the whole board in one phase).
+static int iteration_core(prl_solver* s, bool closing_eval, int avg_pair = PRL_FHP_AVG_NORMAL, int avg_pair_b = -1) {
     if (s->fused && s->user_strategy_f64 >= 0) { prl_set_error("call reset() / fill_uniform() before iterating after set_strategy()"); return PRL_ERR_STATE; }
     int mode = 0;
     double m_old = 0., m_new = 0.;
@@ -1913,14 +1915,18 @@ static int iteration_core(prl_solver* s, bool closing_eval, int avg_pair = PRL_F
     s->fp.avg_mode = mode;
     s->fp.m_old = m_old;
     s->fp.m_new = m_new;
+    const bool split = avg_pair_b >= 0 && avg_pair_b != avg_pair;
+    if (avg_pair_b < 0) avg_pair_b = avg_pair;
     s->fp.avg_pair = avg_pair;
+    s->fp.avg_pair_b = avg_pair_b;
     s->fp.m_old_prev = s->fp.m_new_prev = 0.;
-    if (avg_pair == PRL_FHP_AVG_CATCH_UP) {
+    if (avg_pair == PRL_FHP_AVG_CATCH_UP || avg_pair_b == PRL_FHP_AVG_CATCH_UP) {
         int mode_prev = 0;
         cfr_plus_weights(s, s->iter - 1, &mode_prev, &s->fp.m_old_prev, &s->fp.m_new_prev);
         if (mode_prev != 2 || mode != 2) { prl_set_error("paired average update outside the blending iterations"); return PRL_ERR_STATE; }
     }
-    if (avg_pair == PRL_FHP_AVG_DEFERRED) s->avg_deferred = true;  // until the catch-up iteration's passes are launched
+    const bool defers = avg_pair == PRL_FHP_AVG_DEFERRED || avg_pair_b == PRL_FHP_AVG_DEFERRED;
+    if (defers) s->avg_deferred = true;  // while either set lacks a step: until the passes of an iteration that defers nothing are launched
     for (int p = 0; p < 2; ++p) {
         bool second_half = false;
         if (s->fused) {
@@ -1951,8 +1957,10 @@ static int iteration_core(prl_solver* s, bool closing_eval, int avg_pair = PRL_F
         if (second_half) s->have_half = true;  // d_half: seat 1's value / best response under the updated strategies
     }
     s->fp.avg_mode = 0;
-    s->fp.avg_pair = PRL_FHP_AVG_NORMAL;
-    if (avg_pair == PRL_FHP_AVG_CATCH_UP) { s->avg_deferred = false; ++s->n_avg_pairs; }
+    s->fp.avg_pair = s->fp.avg_pair_b = PRL_FHP_AVG_NORMAL;
+    s->avg_deferred = defers;
+    if (avg_pair == PRL_FHP_AVG_CATCH_UP) ++s->n_avg_pairs;
+    if (split && avg_pair_b == PRL_FHP_AVG_CATCH_UP) ++s->n_avg_split_pairs;
     if (s->sorted) blocked_avg_step(s, mode, m_old, m_new);
     s->iter += 1;
     if (s->fused && !closing_eval) {
@@ -2121,18 +2129,29 @@ int32_t prl_solver_iterations(prl_solver_t* s, int32_t n) {
     // one iteration t + 1 plays, so t leaves the float64 columns alone and t + 1 applies both steps in registers (prl_fhp_pass.inc, FhpCtxT) -- one
     // HBM round trip of the average per pair. Pairs never span calls: nothing is pending when this returns, a leftover last iteration runs the
     // plain pass. PRL_FHP_NO_AVG_PAIR (read at every call, so that one solver object can be timed both ways) turns it off.
+    // SPLIT PAIRS: a catch-up launch waits on HBM while the deferred launch after it leaves 40 % of HBM idle, and launches cannot overlap. So the pairs
+    // of a seat's set-B nodes (prl_fhp_pass.inc: fhp_avg_set, about half its columns) run one iteration behind set A's, which keep the rule above:
+    // with r counted from the call's first pairable iteration, A defers at even r and catches up at odd r, B stays unpaired at r = 0, defers at odd r
+    // and catches up at even r -- every launch in between moves half a seat's float64 columns. The call's last iteration closes whatever is open
+    // (a set that would defer runs unpaired), so nothing is pending when the call returns either. PRL_FHP_NO_AVG_SPLIT (read at every call) keeps the
+    // whole board in one phase, as do shapes whose pair kinds would spill registers (prl_fhp_avg_split_supported: FHP21).
     const bool may_pair = s->fused && !s->streets && s->variant == PRL_CFR_PLUS && !s->avg_f32 && !getenv("PRL_FHP_NO_AVG_PAIR");
-    bool deferred = false;
+    const bool may_split = may_pair && prl_fhp_avg_split_supported(s->fp.shape) && !getenv("PRL_FHP_NO_AVG_SPLIT");
+    int r = -1;  // iterations of this call since its first pairable one
     for (int i = 0; i < n; ++i) {
-        int avg_pair = PRL_FHP_AVG_NORMAL;
-        if (deferred) avg_pair = PRL_FHP_AVG_CATCH_UP;
+        if (r >= 0) ++r;
         else if (may_pair && i + 1 < n && s->src[0] == PRL_SRC_REGRET && s->src[1] == PRL_SRC_REGRET && s->user_strategy_f64 < 0) {
             int mode; double m_old, m_new;
             cfr_plus_weights(s, s->iter, &mode, &m_old, &m_new);
-            if (mode == 2) avg_pair = PRL_FHP_AVG_DEFERRED;  // (mode 2 holds for every later iteration)
+            if (mode == 2) r = 0;  // (mode 2 holds for every later iteration)
         }
-        TRY(iteration_core(s, i == n - 1, avg_pair));
-        deferred = avg_pair == PRL_FHP_AVG_DEFERRED;
+        const bool last = i == n - 1;
+        int avg_pair = PRL_FHP_AVG_NORMAL, avg_pair_b = -1;
+        if (r >= 0) {
+            avg_pair = r % 2 ? PRL_FHP_AVG_CATCH_UP : last ? PRL_FHP_AVG_NORMAL : PRL_FHP_AVG_DEFERRED;
+            if (may_split) avg_pair_b = r == 0 ? PRL_FHP_AVG_NORMAL : r % 2 ? (last ? PRL_FHP_AVG_NORMAL : PRL_FHP_AVG_DEFERRED) : PRL_FHP_AVG_CATCH_UP;
+        }
+        TRY(iteration_core(s, last, avg_pair, avg_pair_b));
     }
     return PRL_OK;
 }
@@ -2491,6 +2510,7 @@ int32_t prl_solver_get(prl_solver_t* s, int32_t field, void* out) {
         case PRL_SF_GRAPH_REPLAY: *(int32_t*)out = s->levels_graph_exec != nullptr; return PRL_OK;
         case PRL_SF_EXCHANGES: *(int64_t*)out = (int64_t)s->n_exchanges; return PRL_OK;
         case PRL_SF_AVG_PAIRS: *(int64_t*)out = (int64_t)s->n_avg_pairs; return PRL_OK;
+        case PRL_SF_AVG_SPLIT_PAIRS: *(int64_t*)out = (int64_t)s->n_avg_split_pairs; return PRL_OK;
         case PRL_SF_VMM_RANGES: {
             int64_t bytes = 0;
 #if !defined(PRL_EMU)
