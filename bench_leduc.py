@@ -4,7 +4,7 @@ These trees fit in L2 (StandardLeduc: 465 nodes, R = 6), so the run is launch / 
 section 8d), just node-updates/s and the CPU oracle beside it. N > 1 GPUs: independent replicas (the
 tree does not shard) -- launch with torch.distributed.run, value = sum over replicas.
 
-    python bench_leduc.py [--game StandardLeduc|DiscretizedNLLeduc|BigLeduc] [--variant plus|vanilla|linear] [--steps K]
+    python bench_leduc.py [--game StandardLeduc|DiscretizedNLLeduc|BigLeduc] [--variant plus|vanilla|linear|discounted] [--steps K]
 """
 import argparse
 import json
@@ -92,16 +92,18 @@ def main():
     if rank == 0:
         r = game_cls.native_rules()
         o = oracle.Oracle({k: tree.field(k) for k in oracle.Oracle.FIELDS}, boards, r.n_hole_cards, r.n_cards, r.n_suits, r.rank_rule)
-        o.cfr_reset({"vanilla": 0, "plus": 1, "linear": 2}[args.variant], 0)
+        # (the oracle and the reference know three variants: Discounted CFR is held against their Linear CFR, whose update moves the same arrays)
+        ref_variant = "linear" if args.variant == "discounted" else args.variant
+        o.cfr_reset({"vanilla": 0, "plus": 1, "linear": 2}[ref_variant], 0)
         t1 = time.perf_counter()
         for _ in range(args.cpu_iters):
             o.cfr_iteration()
-        out["cpu_baseline"] = {"value": tree.n_nodes * args.cpu_iters / (time.perf_counter() - t1), "unit": "node-updates/s", "cores": 1,
+        out["cpu_baseline"] = {"variant": ref_variant, "value": tree.n_nodes * args.cpu_iters / (time.perf_counter() - t1), "unit": "node-updates/s", "cores": 1,
                                "kind": "port", "sample": "oracle/prl_oracle.c, %d iterations of the same tree" % args.cpu_iters,
                                # the reference's own cfr.iteration() on this game (it runs the Leduc family), timed by scripts/time_reference.py
                                "reference_python_node_updates_per_s": bench_ref.figure("cfr_iteration", "%s/%s" % (
                                    "DiscretizedNLLeduc_POT_ONLY" if args.game == "DiscretizedNLLeduc" else args.game,
-                                   {"plus": "CFRPlus", "vanilla": "VanillaCFR", "linear": "LinearCFR"}[args.variant]), "node_updates_per_s"),
+                                   {"plus": "CFRPlus", "vanilla": "VanillaCFR", "linear": "LinearCFR"}[ref_variant]), "node_updates_per_s"),
                                "reference_timing_source": bench_ref.SOURCE, "reference_timing_host": bench_ref.host()}
         print(json.dumps(out), flush=True)
     if dist is not None:

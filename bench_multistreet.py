@@ -78,6 +78,9 @@ def cpu_baseline(n_iters, game_cls, stack, bets):
             "sample": "CFR+ delay 0, %s 1 flop x 1 turn x 1 river (%d nodes), %d iterations, oracle/prl_oracle.c, 1 thread, %.1f s" % (game_cls.__name__, t.n_nodes, n_iters, dt)}
 
 
+VARIANT_LABEL = {"plus": "CFR+", "vanilla": "Vanilla CFR", "linear": "Linear CFR", "discounted": "Discounted CFR"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--flops", type=int, default=4)
@@ -86,6 +89,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--engine", default="auto")
+    ap.add_argument("--variant", default="plus", choices=["plus", "vanilla", "linear", "discounted"], help="the CFR variant compiled into the kernels "
+                    "(discounted: DCFR with the library's default alpha, beta, gamma = 1.5, 0, 2); the CPU baseline is the oracle's CFR+ and is left out otherwise")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--avg-f32", action="store_true", help="OPT-IN, not the reference's numerics: the street columns' running average stored as float32 "
                     "(PRL_SOLVER_AVG_F32, on this engine since round 5); a second line, config.avg_dtype says so")
@@ -154,13 +159,13 @@ def main():
         if emu_lib:
             from pokerrl_amd.dist import TorchExchange
             exchange = TorchExchange("cpu")
-            s = _native.NativeSolver(tree, "plus", 0, shard=(world, rank, exchange), _lib=lib)
+            s = _native.NativeSolver(tree, args.variant, 0, shard=(world, rank, exchange), _lib=lib)
         else:
             from pokerrl_amd.dist import rccl_shard
-            s = _native.NativeSolver(tree, "plus", 0, shard=rccl_shard(world, rank))
+            s = _native.NativeSolver(tree, args.variant, 0, shard=rccl_shard(world, rank))
     else:
         avg_dtype = "f32" if args.avg_f32 else "f64"
-        s = _native.NativeSolver(tree, "plus", 0, engine=args.engine, _lib=lib, avg_dtype=avg_dtype)
+        s = _native.NativeSolver(tree, args.variant, 0, engine=args.engine, _lib=lib, avg_dtype=avg_dtype)
         if args.placement_candidates > 1 and not emu_lib and s.engine == "fused":
             # as bench.py's placement probe: solver objects of one process differ by ~7 % on this tree, repeatably per object, with where their
             # arrays land physically (scripts/ms_placement_probe.py: 2.38 .. 2.54 ms per iteration). 4 GB each: build a few, keep the fastest,
@@ -172,7 +177,7 @@ def main():
             cands = [(probe(s), s)]
             try:
                 for _ in range(args.placement_candidates - 1):
-                    c = _native.NativeSolver(tree, "plus", 0, engine=args.engine, _lib=lib, avg_dtype=avg_dtype)
+                    c = _native.NativeSolver(tree, args.variant, 0, engine=args.engine, _lib=lib, avg_dtype=avg_dtype)
                     cands.append((probe(c), c))
             except _native.NativeError as e:
                 sys.stderr.write("bench_multistreet.py: placement probe cut short (%s)\n" % e)
@@ -212,11 +217,11 @@ def main():
     achieved = (bytes_last * args.steps / (pass_ms * 1e-3) if fused else bytes_iter * args.steps / (dev_ms * 1e-3)) / 1e9
     per_col, traffic_src = pmc_traffic(args.game, args.flops, args.turns, args.rivers, args.bets)
     out = {
-        "metric": "CFR+ node-updates/sec on a multi-street %s public tree" % args.game, "value": n_nodes_job * args.steps / dt, "unit": "node-updates/s",
+        "metric": "%s node-updates/sec on a multi-street %s public tree" % (VARIANT_LABEL[args.variant], args.game), "value": n_nodes_job * args.steps / dt, "unit": "node-updates/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic", "build_flavor": (lib or _native.lib()).prl_build_flavor().decode(),
         "config": {"avg_dtype": "f32 (opt-in: PRL_SOLVER_AVG_F32; the reference's average is float64)" if args.avg_f32 else "f64",
-                   "workload": "CFR+ (delay 0) on %s (%d-chip stacks%s), %d flops per GPU x %d turns x %d rivers of seeded run-outs, 1326-hand ranges"
+                   "workload": VARIANT_LABEL[args.variant] + " (delay 0) on %s (%d-chip stacks%s), %d flops per GPU x %d turns x %d rivers of seeded run-outs, 1326-hand ranges"
                                % (args.game, stack, (", pot-sized raises" if args.bets == "POT_ONLY" else ", bet_sets.%s raises" % args.bets) if nl else "", args.flops, args.turns, args.rivers),
                    "engine": s.engine + (" (per-street)" if s.engine == "fused" else ""), "nodes": tree.n_nodes, "nodes_whole_job": n_nodes_job,
                    "placement_probe_ms_per_iteration": placement, "flops_per_gpu": args.flops, "exchanges": int(s.get("exchanges")[0]) if (world > 1 or force) else 0, "action_columns": tree.n_cols,
@@ -234,7 +239,7 @@ def main():
                      "frac_whole_iteration": bytes_iter * args.steps / (dev_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS},
     }
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if not args.no_cpu_baseline and world == 1 and args.variant == "plus":
             out["cpu_baseline"] = cpu_baseline(args.cpu_iters, game_cls, stack, bets)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -319,7 +319,7 @@ int32_t prl_env_random_rollout_full_host(const PrlGame* game, const PrlRules* ru
 /* ---------------------------------------------------------------------------------------------------------------- */
 typedef struct prl_solver prl_solver_t;
 
-enum { PRL_VARIANT_VANILLA = 0, PRL_VARIANT_PLUS = 1, PRL_VARIANT_LINEAR = 2 };
+enum { PRL_VARIANT_VANILLA = 0, PRL_VARIANT_PLUS = 1, PRL_VARIANT_LINEAR = 2, PRL_VARIANT_DISCOUNTED = 3 };
 
 /* create = upload tree + build showdown plans + CFRBase.reset(); `delay` is CFR+'s linear-averaging delay */
 int32_t prl_solver_create(const prl_tree_t* tree, int32_t variant, int32_t delay, prl_solver_t** out_solver);
@@ -427,6 +427,21 @@ int32_t prl_chance_sum_host(const float* board_values, int32_t n_boards, int32_t
 int32_t prl_chance_sum_host_ragged(const float* board_values, int32_t n_boards, int32_t R, int32_t world_size, int32_t shard_boards, float* out);
 void prl_solver_destroy(prl_solver_t* solver);
 int32_t prl_solver_reset(prl_solver_t* solver);                        /* _CFRBase.reset            :110-120 */
+/* DISCOUNTED CFR (PRL_VARIANT_DISCOUNTED; Brown & Sandholm 2019 -- the reference has no such class). With the 0-based iteration counter t >= 1,
+ * float32 arithmetic, separate multiply and add:
+ *     regret  = (ev_action - ev_node) + (old > 0 ? d_pos : d_neg) * old        d_pos = t^alpha / (t^alpha + 1), d_neg = t^beta / (t^beta + 1)
+ *     avg_sum = d_avg * avg_sum + strategy * reach                            d_avg = (t / (t + 1))^gamma
+ * and iteration 0 stores the instantaneous regrets / the first contribution as every variant does. Regrets are stored unclamped, regret matching
+ * clamps at 0, the average is avg_sum normalised (Vanilla's / Linear's code). `delay` is ignored. The three factors of an iteration are computed in
+ * float64 on the HOST by prl_dcfr_factors and rounded to float32 once; every engine takes them from there (as kernel arguments, or from a device
+ * table the host filled), so all engines agree to the last bit. out3 = (d_pos, d_neg, d_avg); iter >= 1; alpha and gamma finite, beta finite or
+ * -inf (negative regrets forgotten from the third iteration on), else PRL_ERR_ARG.
+ * A solver is created with (alpha, beta, gamma) = (1.5, 0, 2). set_discount changes them while the iteration counter is 0 (after create / reset;
+ * PRL_ERR_STATE otherwise; PRL_ERR_UNSUPPORTED on a solver of another variant); reset keeps them; a checkpoint carries them and load_state refuses a
+ * blob saved with other values. */
+int32_t prl_dcfr_factors(int32_t iter, double alpha, double beta, double gamma, float out3[3]);
+int32_t prl_solver_set_discount(prl_solver_t* solver, double alpha, double beta, double gamma);
+int32_t prl_solver_get_discount(prl_solver_t* solver, double* out_alpha, double* out_beta, double* out_gamma);
 int32_t prl_solver_iteration(prl_solver_t* solver);                    /* _CFRBase.iteration        :122-134 (w/o avg eval) */
 int32_t prl_solver_iterations(prl_solver_t* solver, int32_t n);
 /* n iterations of MANY independent solvers in one launch, one workgroup (one CU) per solver: the way to fill a GPU with

@@ -598,7 +598,18 @@ OBS_VANILLA, OBS_HISTORY, OBS_FLAT_HU_LIMIT = 0, 1, 2
 # solver field ids (include/pokerrl_hip.h)
 SF = dict(reach=0, ev=1, ev_br=2, strategy=3, strat_f64=4, regret=5, avg=6, avg_f64=7, avg_sum=8, br_idx=9,
           expl_history=10, iter=11, constants=12, bytes_allocated=13, engine=14, graph_replay=15, explicit_strategy=16, exchanges=17, vmm_ranges=18, avg_pairs=19, avg_split_pairs=20)
-VARIANTS = {"vanilla": 0, "plus": 1, "linear": 2}
+VARIANTS = {"vanilla": 0, "plus": 1, "linear": 2, "discounted": 3}
+
+
+def dcfr_factors(iter, alpha, beta, gamma, _lib=None):
+    """Discounted CFR's float32 factors (d_pos, d_neg, d_avg) of the 0-based iteration `iter` >= 1, from the one host function every engine takes
+    them from (prl_dcfr_factors): t^alpha / (t^alpha + 1), t^beta / (t^beta + 1), (t / (t + 1))^gamma in float64, rounded once."""
+    L = _lib or lib()
+    L.prl_dcfr_factors.argtypes = [ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_float)]
+    L.prl_dcfr_factors.restype = ctypes.c_int32
+    out = (ctypes.c_float * 3)()
+    check(L.prl_dcfr_factors(int(iter), float(alpha), float(beta), float(gamma), out), L)
+    return np.array([out[0], out[1], out[2]], np.float32)
 ENGINES = {"auto": 0, "levels": 1, "fused": 2}
 
 
@@ -612,13 +623,14 @@ class NativeSolver:
     boards, the last one the rest (prl_solver_create_sharded_ragged)."""
 
     def __init__(self, tree, variant, delay=0, engine="auto", _lib=None, shard=None, avg_dtype="f64", place=None, probe_iters=4, board_mult=None,
-                 symmetrize=False):
+                 symmetrize=False, discount=None):
         """place=k (unsharded solves): placement selection -- the library builds up to k solvers side by side, times probe_iters steady-state
         iterations of each and keeps the fastest (prl_solver_create_placed; .placement_ms / .placement_chosen say what it saw).
         board_mult=int array [n_boards] (+ symmetrize=True): weighted boards / suit isomorphism (prl_solver_create_weighted) -- the listed boards
         stand for board_mult[i] boards each; with symmetrize they are suit-class representatives (pokerrl_amd.game.board_enum.
         single_deal_board_classes) and the chance node's values are averaged over every hand's suit orbit: the WHOLE game from its classes.
-        The library checks that claim (representatives, orbit sizes, the whole game covered); symmetrize="subset" admits a subset of the classes."""
+        The library checks that claim (representatives, orbit sizes, the whole game covered); symmetrize="subset" admits a subset of the classes.
+        discount=(alpha, beta, gamma): variant "discounted" only -- Discounted CFR's parameters (prl_solver_set_discount; default 1.5, 0, 2)."""
         self._L = _lib or tree._L
         self.placement_ms, self.placement_chosen = None, None
         if _lib is None and self._L is lib():
@@ -707,6 +719,8 @@ class NativeSolver:
             check(self._L.prl_solver_get_stream(self._h, ctypes.byref(sp)), self._L)
             if shard[2].bind_stream(sp.value or 0):
                 check(self._L.prl_solver_set_exchange_async(self._h, 1), self._L)
+        if discount is not None:  # after whichever create path ran: every one of them hands back a solver at iteration 0
+            self.set_discount(*discount)
         self.n_nodes, self.n_cols, self.R = tree.n_nodes, tree.n_cols, tree.range_size
         eng = np.zeros(1, np.int32)
         self._call("prl_solver_get", SF["engine"], _ptr(eng))
@@ -725,6 +739,21 @@ class NativeSolver:
 
     def reset(self):
         self._call("prl_solver_reset")
+
+    def set_discount(self, alpha, beta, gamma):
+        """Discounted CFR's parameters; only while the iteration counter is 0 (after create / reset)"""
+        self._L.prl_solver_set_discount.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double]
+        self._L.prl_solver_set_discount.restype = ctypes.c_int32
+        self._call("prl_solver_set_discount", float(alpha), float(beta), float(gamma))
+
+    @property
+    def discount(self):
+        """(alpha, beta, gamma) of a Discounted CFR solver"""
+        a, b, g = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        self._L.prl_solver_get_discount.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_double)] * 3
+        self._L.prl_solver_get_discount.restype = ctypes.c_int32
+        self._call("prl_solver_get_discount", ctypes.byref(a), ctypes.byref(b), ctypes.byref(g))
+        return (a.value, b.value, g.value)
 
     def iteration(self):
         self._call("prl_solver_iteration")

@@ -6,7 +6,7 @@ names and logged scalars (exploitability of the current and of the average strat
 One `iteration()` = both seats updated (EV -> regrets -> regret matching -> reach -> average), EVs recomputed, current
 strategy exploitability logged, average strategy evaluated (_CFRBase.py:122-134) -- all as HIP kernels behind
 `pokerrl_amd._native.NativeSolver`; nothing is computed in Python. The regret / averaging formulas of the three built-in variants
-are compiled into the kernels (VanillaCFR.py, CFRPlus.py, LinearCFR.py).
+are compiled into the kernels (VanillaCFR.py, CFRPlus.py, LinearCFR.py), and so is Discounted CFR (DiscountedCFR.py; no reference class).
 
 Other variants: a subclass that leaves `_VARIANT = None` and implements the reference's protected hooks `_regret_formula_first_it`,
 `_regret_formula_after_first_it`, `_compute_new_strategy`, `_add_strategy_to_average` (_CFRBase.py:140-144,187-196) exactly as it
@@ -31,7 +31,7 @@ class CFRBase:
     _VARIANT = None
 
     def __init__(self, name, chief_handle, game_cls, agent_bet_set, algo_name, starting_stack_sizes=None, delay=0, boards=None,
-                 engine="auto", n_boards=None, max_outcomes=None, board_seed=None, suit_isomorphism=None):
+                 engine="auto", n_boards=None, max_outcomes=None, board_seed=None, suit_isomorphism=None, discount=None):
         self._name = name
         self._n_seats = 2
         self._chief_handle = chief_handle
@@ -52,14 +52,14 @@ class CFRBase:
             board_mult = None
         if board_mult is not None and self._host_hooks:
             raise ValueError("a CFR variant written against the reference's hook methods runs on per-node vectors (LEVELS engine): give it boards= / "
-                             "n_boards=; the whole game through its suit classes needs a built-in variant (CFRPlus / LinearCFR / VanillaCFR)")
+                             "n_boards=; the whole game through its suit classes needs a built-in variant (CFRPlus / LinearCFR / VanillaCFR / DiscountedCFR)")
         self._boards, self._engine = boards, engine
         self._trees = [PublicTree(env_bldr=b, stack_size=a.starting_stack_sizes_list, stop_at_street=None, boards=boards, engine=engine, board_mult=board_mult,
                                   suit_isomorphism=True if board_mult is not None else None)  # (the classes of the whole game, as enumerated above)
                        for b, a in zip(self._env_bldrs, self._env_args)]
         self._eval_trees = None
         for tree in self._trees:
-            tree.build_tree(variant="vanilla" if self._host_hooks else self._VARIANT, delay=delay)
+            tree.build_tree(variant="vanilla" if self._host_hooks else self._VARIANT, delay=delay, discount=discount)  # (discount: Discounted CFR's alpha, beta, gamma)
             print("Tree with stack size", tree.stack_size, "has", tree.n_nodes, "nodes out of which", tree.n_nonterm, "are non-terminal.")
         self._algo_name = algo_name
         c = chief_handle.create_experiment

@@ -1,0 +1,1 @@
+from pokerrl_amd.cfr.DiscountedCFR import DiscountedCFR  # noqa: F401

@@ -30,8 +30,10 @@ enum { PRL_PREFLOP = 0, PRL_FLOP = 1, PRL_TURN = 2, PRL_RIVER = 3 };
 // node kinds of the flat public tree
 enum { PRL_NODE_DECISION = 0, PRL_NODE_CHANCE = 1, PRL_NODE_TERM_FOLD = 2, PRL_NODE_TERM_SHOWDOWN = 3 };
 
-// CFR variants (reference: PokerRL/cfr/{VanillaCFR,CFRPlus,LinearCFR}.py)
-enum { PRL_CFR_VANILLA = 0, PRL_CFR_PLUS = 1, PRL_CFR_LINEAR = 2 };
+// CFR variants (reference: PokerRL/cfr/{VanillaCFR,CFRPlus,LinearCFR}.py; Discounted CFR has no reference class: pokerrl_hip.h, prl_dcfr_factors)
+enum { PRL_CFR_VANILLA = 0, PRL_CFR_PLUS = 1, PRL_CFR_LINEAR = 2, PRL_CFR_DISCOUNTED = 3 };
+// Discounted CFR's three float32 factors of one iteration (host: prl_dcfr_factors; all zero for the other variants and for iteration 0)
+struct PrlDcfr { float pos, neg, avg; };
 
 // status codes, PrlRules, PrlGame and every exported prototype live in the public C header
 #include "pokerrl_hip.h"

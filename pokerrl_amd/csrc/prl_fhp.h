@@ -235,6 +235,9 @@ struct PrlFhpParams {
     // follows q's pass -- so it rides on the next pass that walks q's reach (phase B for seat q): bit q of avgsum_mask
     float* avg_sum;             // board region: node.data["avg_strat_sum"] (VanillaCFR.py:40-55, LinearCFR.py:41-57)
     int32_t avgsum_mask, avgsum_iter[2];
+    // Discounted CFR (host: prl_dcfr_factors): the regret factors of iteration `iter`, and per seat the average factor of ITS deferred iteration
+    // avgsum_iter[q] -- the seat whose update is applied one walk late belongs to an earlier iteration than the one under way
+    float dcfr_pos, dcfr_neg, dcfr_avg[2];
     int32_t block_sum;          // 1: board_out holds one row per PRL_CHANCE_BLOCK boards (level 0 of the chance sum done by the pass)
     int32_t exp;                // FHP_EXPERIMENT builds: run-time switch between two code paths (prl_debug_set_experiment)
     int32_t no_steady;          // tests: 1 = never take the CFR+ steady-state specialisation of the pass (prl_fhp_pass.inc, FhpCtxT)

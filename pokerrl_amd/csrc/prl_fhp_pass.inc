@@ -281,7 +281,7 @@ constexpr bool fhp_may_load_avg(int steady, int n) {
     const int k = fhp_set_kind(steady, fhp_avg_set(n));
     return k == 1 || k == 4 || k == 6;
 }
-template <int STEADY>  // 0 generic; 1 CFR+, 2 Linear CFR, 3 vanilla CFR in their steady state; 4 CFR+ with the float32 average; 5 / 6 CFR+ deferred / catch-up;
+template <int STEADY>  // 0 generic; 1 CFR+, 2 Linear CFR, 3 vanilla CFR, 7 Discounted CFR in their steady state; 4 CFR+ with the float32 average; 5 / 6 CFR+ deferred / catch-up;
                        // fhp_steady_pair(ka, kb): CFR+ with set A under kind ka and set B under kb
 struct FhpCtxT {
     static constexpr int steady = STEADY;
@@ -295,6 +295,7 @@ struct FhpCtxT {
         if constexpr (fhp_steady_plus(STEADY)) return PRL_CFR_PLUS;
         else if constexpr (STEADY == 2) return PRL_CFR_LINEAR;
         else if constexpr (STEADY == 3) return PRL_CFR_VANILLA;
+        else if constexpr (STEADY == 7) return PRL_CFR_DISCOUNTED;
         else return variant_;
     }
     PRL_DEV PRL_INLINE bool first_iteration() const { if constexpr (STEADY != 0) return false; else return iter == 0; }
@@ -441,7 +442,8 @@ struct FhpDown {
                         for (int k = 0; k < FHP_SLOTS; ++k) {
                             float contrib = (float)s[i][k] * rq.v[k];
                             if (c.variant() == PRL_CFR_LINEAR) contrib = contrib * (float)(it + 1);
-                            as[k] = it > 0 ? AP.v[col0 + i][k] + contrib : contrib;
+                            if (c.variant() == PRL_CFR_DISCOUNTED) as[k] = it > 0 ? (c.prm->dcfr_avg[Q] * AP.v[col0 + i][k]) + contrib : contrib;
+                            else as[k] = it > 0 ? AP.v[col0 + i][k] + contrib : contrib;
                         }
                         fhp_gstore(c.prm->avg_sum + c.cofs + (size_t)(col0 + i) * FHP_NP, as);
                     }
@@ -752,7 +754,11 @@ struct FhpUp {
                         if (!c.first_iteration()) {
                             FhpF old;
                             for (int k = 0; k < FHP_SLOTS; ++k) old[k] = SRC == PRL_SRC_REGRET ? R.rg[col0 + i][k] : 0.f;  // untouched regrets are 0
-                            rv = c.variant() == PRL_CFR_LINEAR ? ((float)(c.iter + 1) * d) + old : d + old;
+                            if (c.variant() == PRL_CFR_DISCOUNTED) {  // old regrets discounted by sign (prl_dcfr_factors)
+                                FhpF w;
+                                for (int k = 0; k < FHP_SLOTS; ++k) w[k] = old[k] > 0.f ? c.prm->dcfr_pos : c.prm->dcfr_neg;
+                                rv = d + (w * old);
+                            } else rv = c.variant() == PRL_CFR_LINEAR ? ((float)(c.iter + 1) * d) + old : d + old;
                         }
                         for (int k = 0; k < FHP_SLOTS; ++k) {
                             float r = rv[k];
@@ -1207,7 +1213,8 @@ int launch_pass(const PrlFhpParams& prm, int mode, int src0, int src1, void* str
                        : (prm.variant == PRL_CFR_PLUS && prm.avg_mode == 2 && prm.avgsum_mask == 0)
                            ? (prm.avg32 ? 4 : fhp_steady_pair(kind_of(prm.avg_pair), kind_of(prm.avg_pair_b)))
                        : (prm.variant == PRL_CFR_LINEAR && prm.avg_mode == 0) ? 2
-                       : (prm.variant == PRL_CFR_VANILLA && prm.avg_mode == 0) ? 3 : 0;
+                       : (prm.variant == PRL_CFR_VANILLA && prm.avg_mode == 0) ? 3
+                       : (prm.variant == PRL_CFR_DISCOUNTED && prm.avg_mode == 0) ? 7 : 0;
     switch (key) {
         case PRL_FHP_UPDATE0 * 100 + PRL_SRC_UNIFORM64 * 10 + PRL_SRC_UNIFORM64: fhp_launch_t<PRL_FHP_UPDATE0, PRL_SRC_UNIFORM64, PRL_SRC_UNIFORM64>(prm, grid, stream); break;
         case PRL_FHP_UPDATE1 * 100 + PRL_SRC_REGRET * 10 + PRL_SRC_UNIFORM64: fhp_launch_t<PRL_FHP_UPDATE1, PRL_SRC_REGRET, PRL_SRC_UNIFORM64>(prm, grid, stream); break;
@@ -1228,6 +1235,7 @@ int launch_pass(const PrlFhpParams& prm, int mode, int src0, int src1, void* str
             else if (steady == fhp_steady_pair(1, 6)) fhp_launch_split_t<PRL_FHP_UPDATE0_BR, fhp_steady_pair(1, 6)>(prm, grid, stream);
             else if (steady == 2) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 2>(prm, grid, stream);
             else if (steady == 3) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 3>(prm, grid, stream);
+            else if (steady == 7) fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET, 7>(prm, grid, stream);
             else fhp_launch_t<PRL_FHP_UPDATE0_BR, PRL_SRC_REGRET, PRL_SRC_REGRET>(prm, grid, stream);
             break;
         case PRL_FHP_UPDATE1_EVAL1 * 100 + PRL_SRC_REGRET * 10 + PRL_SRC_REGRET:
@@ -1242,6 +1250,7 @@ int launch_pass(const PrlFhpParams& prm, int mode, int src0, int src1, void* str
             else if (steady == fhp_steady_pair(1, 6)) fhp_launch_split_t<PRL_FHP_UPDATE1_EVAL1, fhp_steady_pair(1, 6)>(prm, grid, stream);
             else if (steady == 2) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 2>(prm, grid, stream);
             else if (steady == 3) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 3>(prm, grid, stream);
+            else if (steady == 7) fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET, 7>(prm, grid, stream);
             else fhp_launch_t<PRL_FHP_UPDATE1_EVAL1, PRL_SRC_REGRET, PRL_SRC_REGRET>(prm, grid, stream);
             break;
         case PRL_FHP_EVAL0 * 100 + PRL_SRC_REGRET * 10 + PRL_SRC_REGRET: fhp_launch_t<PRL_FHP_EVAL0, PRL_SRC_REGRET, PRL_SRC_REGRET>(prm, grid, stream); break;

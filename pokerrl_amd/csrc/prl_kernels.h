@@ -14,10 +14,10 @@ void prl_launch_terminals(const PrlDevTree& T, const PrlDevState& S, const int32
 void prl_launch_ev_levels(const PrlDevTree& T, const PrlDevState& S, const int32_t* h_level_start, void* stream, float* d_expl_copy = nullptr);
 void prl_launch_ev(const PrlDevTree& T, const PrlDevState& S, const int32_t* h_level_start, const int32_t* d_term_nodes, int n_term,
                    void* stream, float* d_expl_copy = nullptr);
-void prl_launch_regret_strategy(const PrlDevTree& T, const PrlDevState& S, const int32_t* d_nodes, int n, int p, int variant, int iter,
+void prl_launch_regret_strategy(const PrlDevTree& T, const PrlDevState& S, const int32_t* d_nodes, int n, int p, int variant, int iter, PrlDcfr dc,
                                 void* stream);
 void prl_launch_average(const PrlDevTree& T, const PrlDevState& S, const int32_t* d_nodes, int n, int p, int variant, int iter, int mode,
-                        double m_old, double m_new, void* stream);
+                        double m_old, double m_new, PrlDcfr dc, void* stream);
 struct PrlIterDev;
 struct PrlSmallJob;  // prl_solver_types.h
 size_t prl_small_state_bytes(const PrlDevTree& T, const PrlDevState& S);

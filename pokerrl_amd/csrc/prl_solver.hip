@@ -9,6 +9,7 @@
 //           the chance node as a leaf; each board subtree is walked on chip by one workgroup (prl_fhp_kernels.hip); the
 //           boards' root values are summed in the canonical nested order into the chance node.
 #include <math.h>
+#include <cmath>
 #include <stdlib.h>
 #include <string.h>
 #if !defined(PRL_EMU)
@@ -48,6 +49,9 @@ struct prl_solver {
     int n_nodes_p[2] = {0, 0};
     int32_t* d_col_node = nullptr;
     int variant = PRL_CFR_PLUS, delay = 0, iter = 0;
+    double dcfr[3] = {1.5, 0., 2.};  // Discounted CFR: alpha, beta, gamma (prl_solver_set_discount)
+    float* d_dcfr_tab = nullptr;     // its factors of iterations [iter, iter + n) for the kernels that count iterations on the device ([PRL_DCFR_TAB_ROWS][3])
+    std::vector<float> h_dcfr_tab;   // ... and the host copy an upload in flight reads
     bool ev_valid = false;    // S.ev / S.ev_br / S.expl correspond to the current strategy + reach
     bool root_reach_set[2] = {false, false};  // the root's reach (a constant) is in place: S / any other state
     float* expl_copy_dst = nullptr;  // where the next evaluation's exploitability goes besides S.expl (its slot of the history)
@@ -391,6 +395,14 @@ static void blocked_avg_step(prl_solver* s, int mode, double m_old, double m_new
         s->blk_avg[A] = a;
     }
 }
+// Discounted CFR: the factors of iteration `iter` (zeros for the other variants and for iteration 0, which discounts nothing)
+static PrlDcfr dcfr_of(const prl_solver* s, int iter) {
+    PrlDcfr dc = {0.f, 0.f, 0.f};
+    if (s->variant != PRL_CFR_DISCOUNTED || iter < 1) return dc;
+    float f[3];
+    if (prl_dcfr_factors(iter, s->dcfr[0], s->dcfr[1], s->dcfr[2], f) == PRL_OK) { dc.pos = f[0]; dc.neg = f[1]; dc.avg = f[2]; }
+    return dc;
+}
 static void cfr_plus_weights(const prl_solver* s, int iter, int* mode, double* m_old, double* m_new) {
     *mode = 0; *m_old = 0.; *m_new = 0.;
     if (s->variant != PRL_CFR_PLUS) return;
@@ -474,12 +486,15 @@ int street_sweep(prl_solver* s, const PrlDevState& st, int mode, int src0, int s
     p.iter = s->iter;
     p.avg_mode = s->fp.avg_mode; p.m_old = s->fp.m_old; p.m_new = s->fp.m_new;  // set by iteration_core for the update passes
     p.avgsum_mask = 0;
+    const PrlDcfr dc = dcfr_of(s, s->iter);
+    p.dcfr_pos = dc.pos; p.dcfr_neg = dc.neg; p.dcfr_avg[0] = p.dcfr_avg[1] = 0.f;
     if (&st == &s->S && strat_arr == nullptr) {  // pending Vanilla / Linear average updates ride on the reach walk of that seat
         const bool walks[2] = {prl_fhp_runs_seat(mode, 1), prl_fhp_runs_seat(mode, 0)};
         for (int q = 0; q < 2; ++q)
             if (walks[q] && s->avg_pending[q] >= 0) {
                 p.avgsum_mask |= 1 << q;
                 p.avgsum_iter[q] = s->avg_pending[q];
+                p.dcfr_avg[q] = dcfr_of(s, s->avg_pending[q]).avg;  // of the iteration whose update was deferred, not of the one under way
                 s->avg_pending[q] = -1;
                 s->board_avg_f64 = true;
                 s->board_avg_stale = true;
@@ -622,6 +637,8 @@ int fused_board_pass(prl_solver* s, const PrlDevState& st, int mode, int src0, i
     p.avg = s->avg_f32 ? nullptr : s->d_avg + s->board_ofs;
     p.avg32 = s->d_avg32 ? s->d_avg32 + s->board_ofs : nullptr;
     p.avgsum_mask = 0;
+    const PrlDcfr dc = dcfr_of(s, s->iter);
+    p.dcfr_pos = dc.pos; p.dcfr_neg = dc.neg; p.dcfr_avg[0] = p.dcfr_avg[1] = 0.f;
     // level 0 of the canonical chance sum inside the pass (one row per 32-board block leaves the chip) whenever whole blocks are
     // what comes next: always without an exchange, and with one when the units exchanged are blocks or groups of blocks
     p.block_sum = (s->block_sum && (!s->exchange || s->xlevel >= 1)) ? 1 : 0;
@@ -631,6 +648,7 @@ int fused_board_pass(prl_solver* s, const PrlDevState& st, int mode, int src0, i
             if (walks[q] && s->avg_pending[q] >= 0) {
                 p.avgsum_mask |= 1 << q;
                 p.avgsum_iter[q] = s->avg_pending[q];
+                p.dcfr_avg[q] = dcfr_of(s, s->avg_pending[q]).avg;  // of the iteration whose update was deferred, not of the one under way
                 s->avg_pending[q] = -1;
                 s->board_avg_f64 = true;
                 s->board_avg_stale = true;
@@ -909,7 +927,7 @@ static int32_t solver_create_impl(const prl_tree_t* tree, int32_t variant, int32
                                   prl_exchange_fn exchange, void* exchange_user, prl_solver_t** out, int64_t shard_boards = 0, int64_t total_boards = 0,
                                   const void* rccl_uid = nullptr, int32_t flags = 0, const int32_t* board_mult = nullptr, int32_t symmetrize = 0) {
     if (!tree || !out) { prl_set_error("NULL argument"); return PRL_ERR_ARG; }
-    if (variant < 0 || variant > 2 || delay < 0 || engine < 0 || engine > 2) { prl_set_error("bad variant / delay / engine"); return PRL_ERR_ARG; }
+    if (variant < 0 || variant > PRL_CFR_DISCOUNTED || delay < 0 || engine < 0 || engine > 2) { prl_set_error("bad variant / delay / engine"); return PRL_ERR_ARG; }
     if (!prl_device_available()) { prl_set_error("no HIP device: the solver has no CPU fallback"); return PRL_ERR_NO_DEVICE; }
     const PrlFlatTree& full = *prl_tree_flat(tree);
     if (full.is_partial) { prl_set_error("partial tree (stop_at_street): structure only, there is nothing to solve below the cut"); return PRL_ERR_UNSUPPORTED; }
@@ -1619,12 +1637,13 @@ struct PrlStateHeader {
 const uint32_t PRL_STATE_VERSION = 3;  // 3: single-deal fused solvers save their column arrays as they hold them (sorted storage)
 const uint32_t PRL_STATE_MAGIC = 0x50524C53u;  // "PRLS"
 
-struct StateLayout { size_t regret, avg, avg_sum, strategy, strat_f64, avg_f64, hist, total; };
+struct StateLayout { size_t dcfr, regret, avg, avg_sum, strategy, strat_f64, avg_f64, hist, total; };
 StateLayout state_layout(const prl_solver* s, int iter) {
     const size_t nc = col_array_elems(s), tc = (size_t)s->T.n_cols * s->R;
     StateLayout L;
     size_t o = sizeof(PrlStateHeader);
     auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
+    L.dcfr = take(s->variant == PRL_CFR_DISCOUNTED ? 3 * sizeof(double) : 0);  // Discounted CFR: alpha, beta, gamma (the other variants' blobs have no such piece)
     L.regret = take(nc * 4); L.avg = take(nc * 8); L.avg_sum = take(s->S.avg_sum ? nc * 4 : 0); L.strategy = take(tc * 8);
     L.strat_f64 = take((size_t)s->T.n_nodes); L.avg_f64 = take((size_t)s->T.n_nodes); L.hist = take((size_t)(iter + 1) * 2 * 4);
     L.total = o;
@@ -1655,6 +1674,10 @@ int32_t prl_solver_save_state(prl_solver_t* s, void* out, uint64_t bytes) {
     h.board_avg_f64 = s->board_avg_f64; h.has_avg_sum = s->S.avg_sum != nullptr;
     char* b = (char*)out;
     memcpy(b, &h, sizeof(h));
+    if (s->variant == PRL_CFR_DISCOUNTED) {
+        memset(b + L.dcfr, 0, L.regret - L.dcfr);
+        memcpy(b + L.dcfr, s->dcfr, sizeof(s->dcfr));
+    }
     const size_t nc = col_array_elems(s), tc = (size_t)s->T.n_cols * s->R;
     PRL_HIP_TRY(hipStreamSynchronize(s->stream));
     PRL_HIP_TRY(hipMemcpy(b + L.regret, s->d_regret, nc * 4, hipMemcpyDeviceToHost));
@@ -1691,6 +1714,10 @@ int32_t prl_solver_load_state(prl_solver_t* s, const void* in, uint64_t bytes) {
     const StateLayout L = state_layout(s, h.iter);
     if (bytes < L.total) { prl_set_error("load_state: truncated blob"); return PRL_ERR_ARG; }
     const char* b = (const char*)in;
+    if (s->variant == PRL_CFR_DISCOUNTED && memcmp(b + L.dcfr, s->dcfr, sizeof(s->dcfr)) != 0) {  // (bit patterns: -inf and signed zeros compare as themselves)
+        prl_set_error("load_state: the blob was saved by a solver with different discount parameters (alpha / beta / gamma)");
+        return PRL_ERR_STATE;
+    }
     const size_t nc = col_array_elems(s), tc = (size_t)s->T.n_cols * s->R;
     TRY(ensure_hist(s, h.iter + 1));
     PRL_HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1764,6 +1791,38 @@ done:
 int32_t prl_chance_sum_host(const float* board_values, int32_t n_boards, int32_t R, int32_t world, float* out) {
     if (world < 1 || n_boards <= 0 || n_boards % world) { prl_set_error("bad argument"); return PRL_ERR_ARG; }
     return prl_chance_sum_host_ragged(board_values, n_boards, R, world, n_boards / world, out);
+}
+
+// Discounted CFR's factors of one iteration: float64 on the host, rounded to float32 once (pokerrl_hip.h). The ONLY place they are computed.
+int32_t prl_dcfr_factors(int32_t iter, double alpha, double beta, double gamma, float out3[3]) {
+    if (!out3) { prl_set_error("NULL argument"); return PRL_ERR_ARG; }
+    if (iter < 1) { prl_set_error("prl_dcfr_factors: iter must be >= 1 (iteration 0 discounts nothing)"); return PRL_ERR_ARG; }
+    if (!std::isfinite(alpha) || !std::isfinite(gamma) || std::isnan(beta) || (std::isinf(beta) && beta > 0)) {
+        prl_set_error("discount parameters: alpha and gamma must be finite, beta finite or -inf");
+        return PRL_ERR_ARG;
+    }
+    const double xa = pow((double)iter, alpha), xb = pow((double)iter, beta);
+    out3[0] = (float)(xa / (xa + 1.0));
+    out3[1] = (float)(xb / (xb + 1.0));
+    out3[2] = (float)pow((double)iter / (double)(iter + 1), gamma);
+    return PRL_OK;
+}
+
+int32_t prl_solver_set_discount(prl_solver_t* s, double alpha, double beta, double gamma) {
+    if (!s) { prl_set_error("NULL solver"); return PRL_ERR_ARG; }
+    if (s->variant != PRL_CFR_DISCOUNTED) { prl_set_error("set_discount: the solver's variant is not Discounted CFR"); return PRL_ERR_UNSUPPORTED; }
+    if (s->iter != 0) { prl_set_error("set_discount: only before the first iteration (after create or reset)"); return PRL_ERR_STATE; }
+    float f[3];
+    TRY(prl_dcfr_factors(1, alpha, beta, gamma, f));  // validates
+    s->dcfr[0] = alpha; s->dcfr[1] = beta; s->dcfr[2] = gamma;
+    return PRL_OK;
+}
+
+int32_t prl_solver_get_discount(prl_solver_t* s, double* out_alpha, double* out_beta, double* out_gamma) {
+    if (!s || !out_alpha || !out_beta || !out_gamma) { prl_set_error("NULL argument"); return PRL_ERR_ARG; }
+    if (s->variant != PRL_CFR_DISCOUNTED) { prl_set_error("get_discount: the solver's variant is not Discounted CFR"); return PRL_ERR_UNSUPPORTED; }
+    *out_alpha = s->dcfr[0]; *out_beta = s->dcfr[1]; *out_gamma = s->dcfr[2];
+    return PRL_OK;
 }
 
 int32_t prl_solver_create(const prl_tree_t* tree, int32_t variant, int32_t delay, prl_solver_t** out) {
@@ -1926,6 +1985,7 @@ static int iteration_core(prl_solver* s, bool closing_eval, int avg_pair = PRL_F
         if (mode_prev != 2 || mode != 2) { prl_set_error("paired average update outside the blending iterations"); return PRL_ERR_STATE; }
     }
     const bool defers = avg_pair == PRL_FHP_AVG_DEFERRED || avg_pair_b == PRL_FHP_AVG_DEFERRED;
+    const PrlDcfr dc = dcfr_of(s, s->iter);  // the trunk's (LEVELS: every) decision node; the board / street passes take theirs in fused_board_pass
     if (defers) s->avg_deferred = true;  // while either set lacks a step: until the passes of an iteration that defers nothing are launched
     for (int p = 0; p < 2; ++p) {
         bool second_half = false;
@@ -1947,11 +2007,11 @@ static int iteration_core(prl_solver* s, bool closing_eval, int avg_pair = PRL_F
                 second_half = true;
             } else TRY(do_compute_ev(s, s->S, p == 0 ? PRL_FHP_UPDATE0 : PRL_FHP_UPDATE1));
         } else TRY(ensure_ev(s));
-        prl_launch_regret_strategy(s->T, s->S, s->d_nodes_p[p], s->n_nodes_p[p], p, s->variant, s->iter, s->stream);
+        prl_launch_regret_strategy(s->T, s->S, s->d_nodes_p[p], s->n_nodes_p[p], p, s->variant, s->iter, dc, s->stream);
         s->src[p] = PRL_SRC_REGRET;
         s->ev_valid = false;
         TRY(do_update_reach(s, s->S));
-        prl_launch_average(s->T, s->S, s->d_nodes_p[p], s->n_nodes_p[p], p, s->variant, s->iter, mode, m_old, m_new, s->stream);
+        prl_launch_average(s->T, s->S, s->d_nodes_p[p], s->n_nodes_p[p], p, s->variant, s->iter, mode, m_old, m_new, dc, s->stream);
         if (s->fused && mode) s->board_avg_f64 = mode == 2;  // the board columns were averaged inside the board pass
         if (s->fused && s->variant != PRL_CFR_PLUS) s->avg_pending[p] = s->iter;  // applied by the next pass that walks seat p
         if (second_half) s->have_half = true;  // d_half: seat 1's value / best response under the updated strategies
@@ -1977,6 +2037,27 @@ static int iteration_core(prl_solver* s, bool closing_eval, int avg_pair = PRL_F
     return record_expl(s);
 }
 
+// Discounted CFR on the paths that count iterations on the device (graph replay, the small-tree kernel, iterations_many): the factors of
+// iterations [s->iter, s->iter + n) as a device table filled from prl_dcfr_factors, so that they are the very floats the per-launch paths pass
+// as kernel arguments. Fills ip's table fields; the caller uploads `ip` and synchronises the stream before anything reads either.
+// Calls of more iterations than the table has rows are split (prl_solver_iterations, prl_solver_iterations_many).
+#define PRL_DCFR_TAB_ROWS 1024
+static int dcfr_table(prl_solver* s, int n, PrlIterDev* ip) {
+    ip->dcfr_tab = nullptr; ip->dcfr_base = 0;
+    if (s->variant != PRL_CFR_DISCOUNTED || n <= 0) return PRL_OK;
+    if (n > PRL_DCFR_TAB_ROWS) { prl_set_error("internal: more iterations than rows of the discount table"); return PRL_ERR_STATE; }
+    if (!s->d_dcfr_tab) TRY(dev_alloc(s, &s->d_dcfr_tab, (size_t)PRL_DCFR_TAB_ROWS * 3));
+    s->h_dcfr_tab.assign((size_t)n * 3, 0.f);
+    for (int k = 0; k < n; ++k) {
+        const PrlDcfr dc = dcfr_of(s, s->iter + k);
+        s->h_dcfr_tab[3 * (size_t)k] = dc.pos; s->h_dcfr_tab[3 * (size_t)k + 1] = dc.neg; s->h_dcfr_tab[3 * (size_t)k + 2] = dc.avg;
+    }
+    // stream-ordered behind whatever still reads the previous rows; the caller's synchronisation after its upload of `ip` covers this one too
+    PRL_HIP_TRY(hipMemcpyAsync(s->d_dcfr_tab, s->h_dcfr_tab.data(), s->h_dcfr_tab.size() * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    ip->dcfr_tab = s->d_dcfr_tab; ip->dcfr_base = s->iter;
+    return PRL_OK;
+}
+
 // LEVELS engine, small 1-hole-card trees: whole iterations inside one single-workgroup kernel (prl_k_small_iterations)
 static int small_tree_iterations(prl_solver* s, int n) {
     TRY(ensure_ev(s));  // an iteration starts from the evaluation that closed the previous one
@@ -1987,6 +2068,7 @@ static int small_tree_iterations(prl_solver* s, int n) {
     memset(&ip, 0, sizeof(ip));
     ip.iter = s->iter;
     ip.hist = s->d_expl_hist;
+    TRY(dcfr_table(s, n, &ip));
     PRL_HIP_TRY(hipMemcpyAsync(s->d_ip, &ip, sizeof(ip), hipMemcpyHostToDevice, s->stream));
     PRL_HIP_TRY(hipStreamSynchronize(s->stream));  // `ip` is a stack variable
     for (int done = 0; done < n;) {
@@ -2014,6 +2096,10 @@ extern "C" int32_t prl_solver_iterations_many(prl_solver_t** solvers, int32_t n_
         for (int j = 0; j < i; ++j) if (solvers[j] == s) { prl_set_error("iterations_many: duplicate solver"); return PRL_ERR_ARG; }
     }
     if (n == 0) return PRL_OK;
+    if (n > PRL_DCFR_TAB_ROWS) {  // (a Discounted CFR solver's factor table holds that many iterations)
+        for (int done = 0; done < n; done += PRL_DCFR_TAB_ROWS) TRY(prl_solver_iterations_many(solvers, n_solvers, n - done < PRL_DCFR_TAB_ROWS ? n - done : PRL_DCFR_TAB_ROWS));
+        return PRL_OK;
+    }
     std::vector<PrlSmallJob> jobs((size_t)n_solvers);
     size_t lds_max = 0;
     for (int i = 0; i < n_solvers; ++i) {
@@ -2026,6 +2112,7 @@ extern "C" int32_t prl_solver_iterations_many(prl_solver_t** solvers, int32_t n_
         memset(&ip, 0, sizeof(ip));
         ip.iter = s->iter;
         ip.hist = s->d_expl_hist;
+        TRY(dcfr_table(s, n, &ip));
         PRL_HIP_TRY(hipMemcpyAsync(s->d_ip, &ip, sizeof(ip), hipMemcpyHostToDevice, s->stream));
         PRL_HIP_TRY(hipStreamSynchronize(s->stream));  // `ip` is a stack variable; the solver's earlier work is complete
         size_t lds = 0;
@@ -2073,6 +2160,7 @@ static int levels_graph_iterations(prl_solver* s, int n) {
     memset(&ip, 0, sizeof(ip));
     ip.iter = s->iter;
     ip.hist = s->d_expl_hist;
+    TRY(dcfr_table(s, n, &ip));
     PRL_HIP_TRY(hipMemcpyAsync(s->d_ip, &ip, sizeof(ip), hipMemcpyHostToDevice, s->stream));
     PRL_HIP_TRY(hipStreamSynchronize(s->stream));  // `ip` is a stack variable
     if (!s->levels_graph_exec) {
@@ -2117,6 +2205,10 @@ int32_t prl_solver_iteration(prl_solver_t* s) {
 // pass. The exploitability history is the same as n single calls produce.
 int32_t prl_solver_iterations(prl_solver_t* s, int32_t n) {
     if (!s) { prl_set_error("NULL solver"); return PRL_ERR_ARG; }
+    if (!s->fused && s->variant == PRL_CFR_DISCOUNTED && n > PRL_DCFR_TAB_ROWS) {  // (dcfr_table: the factor table holds that many iterations)
+        for (int done = 0; done < n; done += PRL_DCFR_TAB_ROWS) TRY(prl_solver_iterations(s, n - done < PRL_DCFR_TAB_ROWS ? n - done : PRL_DCFR_TAB_ROWS));
+        return PRL_OK;
+    }
     if (!s->fused && s->small_tree && n > 0) return small_tree_iterations(s, n);
 #if !defined(PRL_EMU)
     if (!s->fused && !s->graphs_off && n > 0) {

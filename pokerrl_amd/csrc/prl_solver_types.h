@@ -12,7 +12,9 @@
 #include "prl_defs.h"
 
 // iteration state of a graph-replayed iteration (prl_tree_kernels.hip: *_dev kernels)
-struct PrlIterDev { int32_t iter, mode; double m_old, m_new; float* hist; };
+// Discounted CFR: `dcfr_tab` holds the host-computed factors (prl_dcfr_factors) of iterations dcfr_base, dcfr_base + 1, ... as [.][3] float32;
+// prl_k_iter_begin / the small-tree kernel copy the row of the iteration under way into `dc` (no device code computes a power)
+struct PrlIterDev { int32_t iter, mode; double m_old, m_new; float* hist; const float* dcfr_tab; int32_t dcfr_base; PrlDcfr dc; };
 
 #define PRL_CHANCE_BLOCK 32   // canonical chance-sum order: blocks of 32 children, groups of 32 blocks
 

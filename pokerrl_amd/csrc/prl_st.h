@@ -78,6 +78,7 @@ struct PrlStParams {
     int32_t avg_mode;            // as PrlFhpParams
     double m_old, m_new;
     int32_t avgsum_mask, avgsum_iter[2];
+    float dcfr_pos, dcfr_neg, dcfr_avg[2];  // Discounted CFR, as PrlFhpParams
     const uint16_t* hole_packed;
     int32_t plan_stride, cl_stride, n_cards;
     const int16_t *plan_pos, *plan_hgs, *plan_hge, *plan_cl;

@@ -319,7 +319,8 @@ struct StDown {
                         for (int k = 0; k < 2; ++k) {
                             float contrib = (float)s[i][k] * rq.v[k];
                             if (c.variant() == PRL_CFR_LINEAR) contrib = contrib * (float)(it + 1);
-                            as[k] = it > 0 ? AP.v[col0 + i][k] + contrib : contrib;
+                            if (c.variant() == PRL_CFR_DISCOUNTED) as[k] = it > 0 ? (c.prm->dcfr_avg[Q] * AP.v[col0 + i][k]) + contrib : contrib;
+                            else as[k] = it > 0 ? AP.v[col0 + i][k] + contrib : contrib;
                         }
                         st_gstore(st_at(c.prm->avg_sum + (c.col_base_i + col0 + i) * (size_t)c.prm->R, c.gofs), as);
                     }
@@ -685,7 +686,11 @@ struct StUp {
                         if (!c.first_iteration()) {
                             FhpF old;
                             for (int k = 0; k < 2; ++k) old[k] = SRC == PRL_SRC_REGRET ? R.rg[col0 + i][k] : 0.f;
-                            rv = c.variant() == PRL_CFR_LINEAR ? ((float)(c.iter + 1) * d) + old : d + old;
+                            if (c.variant() == PRL_CFR_DISCOUNTED) {  // old regrets discounted by sign (prl_dcfr_factors)
+                                FhpF w;
+                                for (int k = 0; k < 2; ++k) w[k] = old[k] > 0.f ? c.prm->dcfr_pos : c.prm->dcfr_neg;
+                                rv = d + (w * old);
+                            } else rv = c.variant() == PRL_CFR_LINEAR ? ((float)(c.iter + 1) * d) + old : d + old;
                         }
                         for (int k = 0; k < 2; ++k) {
                             float r = rv[k];

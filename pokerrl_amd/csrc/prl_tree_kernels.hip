@@ -582,7 +582,7 @@ PRL_DEV PRL_INLINE void prl_exploitability_body(const PrlDevTree& T, const PrlDe
 // CFR updates of one seat
 // ---------------------------------------------------------------------------------------------------------------------
 PRL_DEV PRL_INLINE void prl_regret_strategy_body(const PrlDevTree& T, const PrlDevState& S, const int32_t* __restrict__ nodes, int n_nodes_p, int p,
-                                                 int variant, int iter) {
+                                                 int variant, int iter, PrlDcfr dc) {
     const size_t total = (size_t)n_nodes_p * T.R;
     for (size_t t = (size_t)prl_bid() * prl_nthreads() + prl_tid(); t < total; t += (size_t)prl_nblocks() * prl_nthreads()) {
         const int node = nodes[t / T.R];
@@ -597,6 +597,7 @@ PRL_DEV PRL_INLINE void prl_regret_strategy_body(const PrlDevTree& T, const PrlD
             float r;
             if (iter == 0) r = d;                                                   // *_first_it
             else if (variant == PRL_CFR_LINEAR) r = ((float)(iter + 1) * d) + *rg;  // LinearCFR.py:27-28
+            else if (variant == PRL_CFR_DISCOUNTED) { const float old = *rg; r = d + ((old > 0.f ? dc.pos : dc.neg) * old); }
             else r = d + *rg;                                                       // VanillaCFR.py:26-27, CFRPlus.py:37-38
             if (variant == PRL_CFR_PLUS) r = r > 0.f ? r : 0.f;
             *rg = r;
@@ -615,7 +616,7 @@ PRL_DEV PRL_INLINE void prl_regret_strategy_body(const PrlDevTree& T, const PrlD
 
 // mode (CFR+ only): 0 nothing yet (iter < delay), 1 copy (iter == delay), 2 blend with the float64 weights m_old / m_new
 PRL_DEV PRL_INLINE void prl_average_body(const PrlDevTree& T, const PrlDevState& S, const int32_t* __restrict__ nodes, int n_nodes_p, int p, int variant,
-                                        int iter, int mode, double m_old, double m_new) {
+                                        int iter, int mode, double m_old, double m_new, PrlDcfr dc) {
     const size_t total = (size_t)n_nodes_p * T.R;
     for (size_t t = (size_t)prl_bid() * prl_nthreads() + prl_tid(); t < total; t += (size_t)prl_nblocks() * prl_nthreads()) {
         const int node = nodes[t / T.R];
@@ -637,7 +638,8 @@ PRL_DEV PRL_INLINE void prl_average_body(const PrlDevTree& T, const PrlDevState&
             const size_t k = prl_cidx(T, col0 + i) + h;
             float contrib = (float)S.strategy[k] * rp;
             if (variant == PRL_CFR_LINEAR) contrib = contrib * (float)(iter + 1);
-            S.avg_sum[k] = iter > 0 ? S.avg_sum[k] + contrib : contrib;
+            if (variant == PRL_CFR_DISCOUNTED) S.avg_sum[k] = iter > 0 ? (dc.avg * S.avg_sum[k]) + contrib : contrib;
+            else S.avg_sum[k] = iter > 0 ? S.avg_sum[k] + contrib : contrib;
         }
         const float s = prl_np_sum([&](int i) { return S.avg_sum[prl_cidx(T, col0 + i) + h]; }, A);
         for (int i = 0; i < A; ++i) {
@@ -681,12 +683,13 @@ PRL_GLOBAL void prl_k_exploitability2(PrlDevTree T, PrlDevState S, float* out2, 
     prl_sync();
     if (prl_tid() < 2) out2b[prl_tid()] = out2[prl_tid()];
 }
-PRL_GLOBAL void prl_k_regret_strategy(PrlDevTree T, PrlDevState S, const int32_t* __restrict__ nodes, int n_nodes_p, int p, int variant, int iter) {
-    prl_regret_strategy_body(T, S, nodes, n_nodes_p, p, variant, iter);
+PRL_GLOBAL void prl_k_regret_strategy(PrlDevTree T, PrlDevState S, const int32_t* __restrict__ nodes, int n_nodes_p, int p, int variant, int iter,
+                                      PrlDcfr dc) {
+    prl_regret_strategy_body(T, S, nodes, n_nodes_p, p, variant, iter, dc);
 }
 PRL_GLOBAL void prl_k_average(PrlDevTree T, PrlDevState S, const int32_t* __restrict__ nodes, int n_nodes_p, int p, int variant, int iter, int mode,
-                              double m_old, double m_new) {
-    prl_average_body(T, S, nodes, n_nodes_p, p, variant, iter, mode, m_old, m_new);
+                              double m_old, double m_new, PrlDcfr dc) {
+    prl_average_body(T, S, nodes, n_nodes_p, p, variant, iter, mode, m_old, m_new, dc);
 }
 
 // ---- graph-replayable flavours: the iteration counter and the CFR+ averaging weights live in device memory, so that one
@@ -705,7 +708,12 @@ PRL_GLOBAL void prl_k_iter_begin(PrlIterDev* ip, int variant, int delay) {
             mode = 2;
         } else if (it == delay) mode = 1;
     }
-    ip->mode = mode; ip->m_old = m_old; ip->m_new = m_new;
+    PrlDcfr dc = {0.f, 0.f, 0.f};
+    if (variant == PRL_CFR_DISCOUNTED && it > 0) {  // the host's table (prl_dcfr_factors), rows from iteration dcfr_base on
+        const float* f = ip->dcfr_tab + 3 * (size_t)(it - ip->dcfr_base);
+        dc.pos = f[0]; dc.neg = f[1]; dc.avg = f[2];
+    }
+    ip->mode = mode; ip->m_old = m_old; ip->m_new = m_new; ip->dc = dc;
 }
 PRL_GLOBAL void prl_k_iter_end(PrlIterDev* ip, const float* __restrict__ expl) {
     if (prl_bid() != 0 || prl_tid() != 0) return;
@@ -716,11 +724,11 @@ PRL_GLOBAL void prl_k_iter_end(PrlIterDev* ip, const float* __restrict__ expl) {
 }
 PRL_GLOBAL void prl_k_regret_strategy_dev(PrlDevTree T, PrlDevState S, const int32_t* __restrict__ nodes, int n_nodes_p, int p, int variant,
                                           const PrlIterDev* __restrict__ ip) {
-    prl_regret_strategy_body(T, S, nodes, n_nodes_p, p, variant, ip->iter);
+    prl_regret_strategy_body(T, S, nodes, n_nodes_p, p, variant, ip->iter, ip->dc);
 }
 PRL_GLOBAL void prl_k_average_dev(PrlDevTree T, PrlDevState S, const int32_t* __restrict__ nodes, int n_nodes_p, int p, int variant,
                                   const PrlIterDev* __restrict__ ip) {
-    prl_average_body(T, S, nodes, n_nodes_p, p, variant, ip->iter, ip->mode, ip->m_old, ip->m_new);
+    prl_average_body(T, S, nodes, n_nodes_p, p, variant, ip->iter, ip->mode, ip->m_old, ip->m_new, ip->dc);
 }
 
 // ---- small trees (1-hole-card games, n_nodes * R of a few thousand: StandardLeduc, DiscretizedNLLeduc): the tree state is
@@ -740,7 +748,8 @@ struct PrlSmallIterArgs {
 // the iteration counter and the CFR+ averaging weights of the iteration under way, in LDS: lane 0 writes them, every lane reads them in every
 // phase -- from the PrlIterDev in HBM that was a round trip per use
 #define PRL_SMALL_IP_BYTES 64
-struct PrlSmallIp { int32_t iter, mode; double m_old, m_new; };
+struct PrlSmallIp { int32_t iter, mode; double m_old, m_new; PrlDcfr dc; };
+static_assert(sizeof(PrlSmallIp) <= PRL_SMALL_IP_BYTES, "PrlSmallIp outgrew its LDS slot");
 // carve the solver state out of LDS (16-byte aligned pieces) and copy it in (dir = 0) or back out (dir = 1)
 PRL_DEV PRL_INLINE size_t prl_small_state_lds(const PrlDevTree& T, const PrlDevState& G, int n_cols, PrlDevState& L, int dir) {  // returns the bytes it took
     char* base = prl_smem();
@@ -843,12 +852,17 @@ PRL_DEV PRL_INLINE void prl_small_iterations_body(const PrlDevTree& TG, const Pr
                     mode = 2;
                 } else if (it == A.delay) mode = 1;
             }
-            IP.iter = it; IP.mode = mode; IP.m_old = m_old; IP.m_new = m_new;
+            PrlDcfr dc = {0.f, 0.f, 0.f};
+            if (A.variant == PRL_CFR_DISCOUNTED && it > 0) {  // as prl_k_iter_begin
+                const float* f = A.ip->dcfr_tab + 3 * (size_t)(it - A.ip->dcfr_base);
+                dc.pos = f[0]; dc.neg = f[1]; dc.avg = f[2];
+            }
+            IP.iter = it; IP.mode = mode; IP.m_old = m_old; IP.m_new = m_new; IP.dc = dc;
         }
         prl_sync();
         for (int p = 0; p < 2; ++p) {
             if (p == 1) prl_small_ev(T, S, A);
-            prl_regret_strategy_body(T, S, A.nodes_p[p], A.n_nodes_p[p], p, A.variant, IP.iter);
+            prl_regret_strategy_body(T, S, A.nodes_p[p], A.n_nodes_p[p], p, A.variant, IP.iter, IP.dc);
             prl_sync();
             prl_reach_root_body(T, S);
             prl_sync();
@@ -856,7 +870,7 @@ PRL_DEV PRL_INLINE void prl_small_iterations_body(const PrlDevTree& TG, const Pr
                 prl_reach_level_body(T, S, A.level_start[d], A.level_start[d + 1] - A.level_start[d]);
                 prl_sync();
             }
-            prl_average_body(T, S, A.nodes_p[p], A.n_nodes_p[p], p, A.variant, IP.iter, IP.mode, IP.m_old, IP.m_new);
+            prl_average_body(T, S, A.nodes_p[p], A.n_nodes_p[p], p, A.variant, IP.iter, IP.mode, IP.m_old, IP.m_new, IP.dc);
             prl_sync();
         }
         prl_small_ev(T, S, A);
@@ -991,14 +1005,14 @@ void prl_launch_ev(const PrlDevTree& T, const PrlDevState& S, const int32_t* h_l
     prl_launch_ev_levels(T, S, h_level_start, stream, d_expl_copy);
 }
 
-void prl_launch_regret_strategy(const PrlDevTree& T, const PrlDevState& S, const int32_t* d_nodes, int n, int p, int variant, int iter,
+void prl_launch_regret_strategy(const PrlDevTree& T, const PrlDevState& S, const int32_t* d_nodes, int n, int p, int variant, int iter, PrlDcfr dc,
                                 void* stream) {
-    if (n > 0) PRL_LAUNCH(prl_k_regret_strategy, prl_grid_for((size_t)n * T.R, 256), 256, 0, stream, T, S, d_nodes, n, p, variant, iter);
+    if (n > 0) PRL_LAUNCH(prl_k_regret_strategy, prl_grid_for((size_t)n * T.R, 256), 256, 0, stream, T, S, d_nodes, n, p, variant, iter, dc);
 }
 
 void prl_launch_average(const PrlDevTree& T, const PrlDevState& S, const int32_t* d_nodes, int n, int p, int variant, int iter, int mode,
-                        double m_old, double m_new, void* stream) {
-    if (n > 0) PRL_LAUNCH(prl_k_average, prl_grid_for((size_t)n * T.R, 256), 256, 0, stream, T, S, d_nodes, n, p, variant, iter, mode, m_old, m_new);
+                        double m_old, double m_new, PrlDcfr dc, void* stream) {
+    if (n > 0) PRL_LAUNCH(prl_k_average, prl_grid_for((size_t)n * T.R, 256), 256, 0, stream, T, S, d_nodes, n, p, variant, iter, mode, m_old, m_new, dc);
 }
 
 // bytes of LDS the whole solver state of a small tree takes (StandardLeduc: ~140 KB); if it fits, the iterations run on it there

@@ -224,9 +224,10 @@ class PublicTree:
         return int(np.sum(self._kind[1:] < KIND_FOLD))
 
     # ---- construction -------------------------------------------------------------------------------------------------
-    def build_tree(self, variant="vanilla", delay=0):
+    def build_tree(self, variant="vanilla", delay=0, discount=None):
+        """discount=(alpha, beta, gamma): variant "discounted" only (Discounted CFR's parameters; None = the library's 1.5, 0, 2)"""
         import copy
-        self._variant, self._delay = variant, delay  # copy() builds its solver the same way
+        self._variant, self._delay, self._discount = variant, delay, discount  # copy() builds its solver the same way
         env_cls, rules = self._env_bldr.env_cls, self._env_bldr.rules
         args = copy.deepcopy(self._env_bldr.env_args)
         args.starting_stack_sizes_list = copy.deepcopy(self._stack_size)
@@ -248,9 +249,9 @@ class PublicTree:
         if self._is_partial:
             self._solver = None
         elif self._board_mult is not None:  # the whole game through its suit classes: fused engine, prl_solver_create_weighted
-            self._solver = _native.NativeSolver(t, variant, delay, board_mult=self._board_mult, symmetrize=self._suit_iso or False)
+            self._solver = _native.NativeSolver(t, variant, delay, board_mult=self._board_mult, symmetrize=self._suit_iso or False, discount=discount)
         else:
-            self._solver = _native.NativeSolver(t, variant, delay, engine=self._engine)
+            self._solver = _native.NativeSolver(t, variant, delay, engine=self._engine, discount=discount)
         self.root = self.node(0)
         self._invalidate()
 
@@ -413,7 +414,7 @@ class PublicTree:
         c = PublicTree(self._env_bldr, self._stack_size, self._stop_at_street if self._is_partial else None,
                        self._put_out_new_round_after_limit, self._is_debugging, self._boards, self._engine,
                        n_boards=n_boards, max_outcomes=max_outcomes, board_seed=board_seed, suit_isomorphism=self._suit_iso, board_mult=self._board_mult)
-        c.build_tree(variant=getattr(self, "_variant", "vanilla"), delay=getattr(self, "_delay", 0))
+        c.build_tree(variant=getattr(self, "_variant", "vanilla"), delay=getattr(self, "_delay", 0), discount=getattr(self, "_discount", None))
         if self._is_partial:  # structure and states only: there is no solver state to move over
             return c
         self._flush()
